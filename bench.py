@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- the fused flash-attention forward on MI355X: fwd ms, achieved TFLOP/s, fraction of the MFMA roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5] [--causal]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5] [--causal] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: inputs, warm-up, ONE timed region of K steps, the JSON line
+(`roofline` and `cpu_baseline` are null in it).  `--full` adds everything else this script measures or checks, as described below: the
+event-timed kernel clock and the roofline built on it (with up to three attempts until the two clocks agree), the validation of the timed
+output, config 5, the side shapes, the graph replay, the CPU baselines.  `--dump-outputs DIR` writes the tensor the last timed step
+produced to DIR/out.npy (float32; a fixed seeded sample of it above DUMP_MAX_ELEMS elements; out_rank<r>.npy per rank when N > 1): the
+inputs are seeded, so two builds of the library can be compared output for output.
 
 Contract (one JSON line on stdout from rank 0):
   * a "step" is one forward over one rank's (batch*heads, N, d) shard of synthetic randn data already resident in
@@ -15,9 +22,9 @@ Contract (one JSON line on stdout from rank 0):
   * `python bench.py --gpus N` with N > 1 works as typed: when it is not already running under torch.distributed.run it
     starts `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD process (before anything here has
     touched a GPU) and relays rank 0's line.  Under torch.distributed.run (RANK / WORLD_SIZE set) it is one rank.
-  * "roofline": dominant kernel's algorithmic FLOP per launch / its mean launch duration measured with HIP events on
+  * "roofline" (--full): dominant kernel's algorithmic FLOP per launch / its mean launch duration measured with HIP events on
     the launch stream (fa_time_forward in the C ABI) against the dense MFMA peak of the pipe that kernel computes on.
-  * "cpu_baseline": PyTorch's CPU SDPA (fp32, scale 1.0 -- the reference bench's own oracle expression,
+  * "cpu_baseline" (--full): PyTorch's CPU SDPA (fp32, scale 1.0 -- the reference bench's own oracle expression,
     bench_flashattention.py:36-40, as BASELINE.md section 3 prescribes) on this box's host cores, on a bounded sample of the
     same workload (rank 0, N = 1 only) -- a reported baseline, not the optimisation target.  The C oracle's timing is
     in `extra.cpu_oracle_port`.
@@ -142,6 +149,27 @@ def make_inputs(bh: int, n: int, d: int, dtype: str, device, seed: int):
     g = torch.Generator(device="cpu").manual_seed(seed)
     # generated on the host in fp32 (as the reference bench does, bench_flashattention.py:31-33), then moved
     return [torch.randn(bh, n, d, generator=g, dtype=torch.float32).to(tdt).to(device) for _ in range(3)]
+
+
+DUMP_MAX_ELEMS = 1 << 23   # float32: 32 MiB per dumped array; a larger output (c5: 2^29 elements) is sampled
+
+
+def dump_output(dirname: str, name: str, t) -> str:
+    """--dump-outputs: `t` (what the last timed step wrote) as float32 in DIR/<name>.npy.  Above DUMP_MAX_ELEMS elements: the elements at
+    DUMP_MAX_ELEMS flat indices drawn once from a fixed seed (sorted; the same indices in every run), gathered on the device."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    flat = t.reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_MAX_ELEMS, dtype=np.int64))
+        flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        arr = flat.float().cpu().numpy()
+    else:
+        arr = t.float().cpu().numpy()
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, np.ascontiguousarray(arr, dtype=np.float32))
+    return path
 
 
 def cpu_oracle_port(total_heads: int, n: int, d: int, causal: bool, scale: float):
@@ -297,8 +325,13 @@ def main():
     ap.add_argument("--accurate", action="store_true",
                     help="bf16 workloads: ask for the fp32 accumulator as output -- FA_KERNEL_AUTO then carries P as two bf16 terms (the accurate path, one launch); "
                          "used by profiles/collect.sh to profile that kernel chain")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the event-timed kernel clock and the roofline, validation of the timed output, "
+                         "config 5, the side shapes, the graph replay, the CPU baselines (a plain run times its K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tensor the last timed step produced to DIR/out.npy (float32; seeded sample when large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for the barrier / max-over-ranks (nccl = RCCL)")
     ap.add_argument("--cpu-stub", action="store_true",
                     help="TEST HOOK (tests/test_distributed_gloo.py): exercise launcher, sharding and timing protocol on CPU ranks with a "
@@ -307,6 +340,11 @@ def main():
                     help="TEST HOOK (tests/test_gpu_dist.py): every rank uses cuda:0 -- two ranks on a one-GPU box (with --backend gloo) exercise "
                          "the world > 1 code of this script; the line says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full
+    if not full:   # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_extras = True
 
     if args.gpus > 1 and not under_launcher():
         # before anything touches a GPU: the ranks are children, this process only relays (never exec from a GPU process)
@@ -353,7 +391,8 @@ def main():
                 torch.cuda.synchronize()
 
     prewarm(step)
-    slow0 = fa.stats()   # (after the warm-up forwards: the kernels' slow-path counters exist from the first forward outside a capture)
+    slow0 = fa.stats() if full else None   # (after the warm-up forwards: the kernels' slow-path counters exist from the first forward outside a capture)
+    # A plain run: ONE timed region of exactly K steps, no second clock.  With --full:
     # The line's two clocks -- K back-to-back forwards from Python between barriers (ms_per_step -> `value`) and the C ABI's event-timed
     # loops on the launch stream (kernel_ms -> `roofline`) -- are taken in ALTERNATION inside one warm state, and when they disagree by more
     # than 2 % (a clock ramp, a noisy neighbour on the box: round 4's line read 4.2 % between them) the pair is measured again, in this
@@ -362,9 +401,14 @@ def main():
     kiters = max(10, min(args.steps, 50))
     attempts = []
     kstats = None
-    for attempt in range(3):
+    dumped = None
+    for attempt in range(3 if full else 1):
         dt = timed_region(step, args.steps, args.warmup if attempt == 0 else 2, torch.cuda.synchronize, world, dist, device)
         per_rank_s = list(PER_RANK_S)
+        if args.dump_outputs:   # what the last timed step of the reported region wrote, before anything else launches into `out`
+            dumped = dump_output(args.dump_outputs, "out" if world == 1 else f"out_rank{rank}", out)
+        if not full:
+            break
         agree = torch.zeros(1, dtype=torch.int32, device=device)
         if rank == 0:
             kstats = time_stats(fa, (q, k, v), reps=5, causal=causal, scale=args.scale, warmup=3, iters=kiters, out=out)
@@ -382,12 +426,15 @@ def main():
     # what the timed launches wrote, checked before anything else runs (rank 0; every rank's shard has the same distribution)
     head_tol = TOLERANCE["f32"] if dtype == "f32" else TOLERANCE["accurate"] if args.accurate else TOLERANCE["bf16_p_bf16_out"]
     head_check = None
-    if rank == 0:
+    if rank == 0 and full:
         head_check = validate_output(fa, q, k, v, out, causal, args.scale, head_tol, f"headline ({args.workload})",
                                      oracle_slab=0 if (world == 1 and not args.no_cpu_baseline) else None)
 
     extras = {"per_rank_ms": per_rank_ms} if world > 1 else {}
-    if rank == 0:
+    if dumped is not None and rank == 0:
+        extras["dumped_output"] = {"file": os.path.basename(dumped), "dtype": "float32",
+                                   "elements": int(min(out.numel(), DUMP_MAX_ELEMS)), "sampled": bool(out.numel() > DUMP_MAX_ELEMS)}
+    if rank == 0 and full:
         extras["timing_attempts"] = attempts
         # what the kernels themselves counted while both clocks ran (fa_read_device_counters): a timed launch that took a slow path -- a tile
         # redone behind a failed optimistic attempt, a workgroup redone in fp32 arithmetic -- would show here
@@ -430,7 +477,7 @@ def main():
 
     # ---- roofline of the dominant kernel: HIP events on the launch stream, inside the C ABI
     roof = None
-    if rank == 0:
+    if rank == 0 and full:
         L = _cabi.lib()
         dt_id = (_cabi.FA_DTYPE_BF16_OUT_F32 if args.accurate else _cabi.FA_DTYPE_BF16) if dtype == "bf16" else _cabi.FA_DTYPE_F32
         kname = L.fa_kernel_name_for(dt_id, d, int(causal), bh, n).decode()
@@ -530,9 +577,11 @@ def main():
                                         "algorithmic_hbm_bytes_per_launch": algorithmic_bytes(bh, n, d, 2) + bh * n * d * 2.0,   # fp32 output: 2 more bytes per element
                                         "what": "same tensors, fp32 output through FA_KERNEL_AUTO (P as bf16 hi + lo, one launch): the figure to "
                                                 "hold against BASELINE.json's '>= 60 % of peak within 1e-3'"}
-        line["validation"] = {"status": "FAILED" if VALIDATION_FAILURES else "ok", "failures": list(VALIDATION_FAILURES),
-                              "what": "every figure that carries max_abs_err was checked on the tensor its timed launches wrote (rung-0 kernel "
-                                      "on the device; headline also against the fp64 CPU oracle); a failure makes this process exit 1"}
+        line["full"] = full
+        if full:
+            line["validation"] = {"status": "FAILED" if VALIDATION_FAILURES else "ok", "failures": list(VALIDATION_FAILURES),
+                                  "what": "every figure that carries max_abs_err was checked on the tensor its timed launches wrote (rung-0 kernel "
+                                          "on the device; headline also against the fp64 CPU oracle); a failure makes this process exit 1"}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

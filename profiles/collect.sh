@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
-BENCH="$R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+BENCH="$R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -- python3 $BENCH > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -- python3 $BENCH > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -- python3 $BENCH > $OUT/pmc_write.log 2>&1
@@ -16,14 +16,14 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY S
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_SALU \
     --kernel-trace -d $OUT/pmc_sq2 -- python3 $BENCH > $OUT/pmc_sq2.log 2>&1
 # the fp32-tensor workload (c3) through the same bench: kernel durations and matrix-pipe / HBM counters of the split kernel
-BENCH3="$R/bench.py --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+BENCH3="$R/bench.py --full --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/stats_c3 -- python3 $BENCH3 > $OUT/stats_c3.log 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES \
     --kernel-trace -d $OUT/pmc_c3_sq -- python3 $BENCH3 > $OUT/pmc_c3_sq.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_c3_fetch -- python3 $BENCH3 > $OUT/pmc_c3_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_c3_write -- python3 $BENCH3 > $OUT/pmc_c3_write.log 2>&1
 # the accurate bf16 path (fp32 output: P as bf16 hi + bf16 lo, ONE launch per forward): durations and matrix-pipe counters
-BENCHA="$R/bench.py --accurate --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+BENCHA="$R/bench.py --full --accurate --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/stats_acc -- python3 $BENCHA > $OUT/stats_acc.log 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES \
     --kernel-trace -d $OUT/pmc_acc_sq -- python3 $BENCHA > $OUT/pmc_acc_sq.log 2>&1
@@ -51,9 +51,9 @@ cd $R
 # which print `traffic` only for the library the counters were collected on -- carry it; the second one at the end checks the kernel names
 python3 profiles/summarize_rocpd.py $OUT $TAG --out $OUT > /dev/null 2>&1 || true
 cp $OUT/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null || true   # (this box's copy of the tree: what bench.py reads)
-python3 bench.py --accurate --no-cpu-baseline --no-extras > $OUT/bench_line_accurate.json 2> $OUT/bench_acc.err
-python3 bench.py --workload c3 --no-cpu-baseline > $OUT/bench_line_c3.json 2> $OUT/bench_c3.err
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --full --accurate --no-cpu-baseline --no-extras > $OUT/bench_line_accurate.json 2> $OUT/bench_acc.err
+python3 bench.py --full --workload c3 --no-cpu-baseline > $OUT/bench_line_c3.json 2> $OUT/bench_c3.err
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
 python3 profiles/summarize_rocpd.py $OUT $TAG --out $OUT || echo "summarize_rocpd.py FAILED (kernel name mismatch?)"
 # the raw rocpd databases are tens of MB per pass (gpurun merges at most 64 MiB back): keep the summaries and the logs only
 find $OUT -mindepth 1 -maxdepth 1 -type d -exec rm -rf {} +

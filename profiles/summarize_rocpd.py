@@ -51,7 +51,7 @@ def main(src: str, tag: str, out: str = None):
     sha = hashlib.sha256(open(lib, "rb").read()).hexdigest() if os.path.exists(lib) else None
     traffic = {"_tag": tag,
                "lib_sha256": sha,   # the binary these passes ran on: bench.py prints `traffic` only while it loads this very library
-               "_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py [--workload c3] --steps 20 --warmup 3 "
+               "_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --full [--workload c3] --steps 20 --warmup 3 "
                           "--no-cpu-baseline --no-extras` (profiles/collect.sh)",
                "_method": "bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 per dispatch of the dominant kernel"}
     bad = []
