@@ -32,14 +32,15 @@ __device__ __forceinline__ float ld(const T* x) { return (float)*x; }
 
 // TIN: element type of Q, K, V (float or __bf16); TOUT: of O.  The arithmetic is fp32 either way.
 template <class TIN, class TOUT>
-__global__ __launch_bounds__(kNaiveWaves * kWave) void fa_naive_f32_kernel(FwdParams p, int d, int causal)
+__global__ __launch_bounds__(kNaiveWaves * kWave) void fa_naive_f32_kernel(FwdParams p, int d, int causal, unsigned block0)
 {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    // one linear grid: slab-major (grid.y stops at 65 535, the ABI admits 2^31 - 1 slabs)
+    // one linear grid: slab-major (grid.y stops at 65 535, the ABI admits 2^31 - 1 slabs); block0: the first block of this launch (launch_naive)
     const int row_blocks = (p.n + kNaiveWaves - 1) / kNaiveWaves;
-    const int row = (int)(blockIdx.x % (unsigned)row_blocks) * kNaiveWaves + wave;
-    const int slab = (int)(blockIdx.x / (unsigned)row_blocks);
+    const unsigned blk = block0 + blockIdx.x;
+    const int row = (int)(blk % (unsigned)row_blocks) * kNaiveWaves + wave;
+    const int slab = (int)(blk / (unsigned)row_blocks);
     if (row >= p.n) return;
 
     const int b = slab / p.heads, h = slab % p.heads;
@@ -93,12 +94,20 @@ hipError_t launch_naive(const FwdParams& p, int d, int causal, int dtype, hipStr
 {
     const int64_t blocks = (int64_t)((p.n + kNaiveWaves - 1) / kNaiveWaves) * p.bh;
     if (blocks > 0x7fffffffLL || d < 1 || d > 256) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(kNaiveWaves * kWave);
-    if (dtype == 0) hipLaunchKernelGGL((fa_naive_f32_kernel<float, float>), grid, block, 0, stream, p, d, causal);
-    else if (dtype == 1) hipLaunchKernelGGL((fa_naive_f32_kernel<__bf16, __bf16>), grid, block, 0, stream, p, d, causal);
-    else if (dtype == 2) hipLaunchKernelGGL((fa_naive_f32_kernel<__bf16, float>), grid, block, 0, stream, p, d, causal);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (dtype < 0 || dtype > 2) return hipErrorInvalidValue;
+    // A launch holds fewer than 2^32 threads (grid x block; a larger one is cut down to the low 32 bits without an error: 262 400 slabs of
+    // 256 rows computed their first 256 slabs and reported success), so more row blocks than that go out as several launches
+    constexpr int64_t kMaxBlocks = 0xffffffffLL / (kNaiveWaves * kWave);
+    const dim3 block(kNaiveWaves * kWave);
+    hipError_t e = hipSuccess;
+    for (int64_t b0 = 0; b0 < blocks && e == hipSuccess; b0 += kMaxBlocks) {
+        const dim3 grid((unsigned)(blocks - b0 < kMaxBlocks ? blocks - b0 : kMaxBlocks));
+        if (dtype == 0) hipLaunchKernelGGL((fa_naive_f32_kernel<float, float>), grid, block, 0, stream, p, d, causal, (unsigned)b0);
+        else if (dtype == 1) hipLaunchKernelGGL((fa_naive_f32_kernel<__bf16, __bf16>), grid, block, 0, stream, p, d, causal, (unsigned)b0);
+        else hipLaunchKernelGGL((fa_naive_f32_kernel<__bf16, float>), grid, block, 0, stream, p, d, causal, (unsigned)b0);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 }  // namespace fa

@@ -30,6 +30,8 @@
  *              stream-ordered pool per device (hipMemPoolCreate; the device's default pool is never touched) --
  *              except while `stream` is capturing, or when the pool fails: the launch then runs unsplit.
  *              (The reference allocates O and a dead O_l inside forward(), flashattention.cu:608-609.)
+ *   memory     reads and writes stay inside the buffers as sized by (bh, n, d); a slab's output depends on that slab's
+ *              rows only; q, k, v, o need 16-byte alignment, lse 4
  *   aliasing   o must not overlap q, k or v (a tile that fails its range check is recomputed from q, k, v after o
  *              was written); overlap is rejected with FA_ERR_INVALID_ARGUMENT
  *   ordering   kernels are enqueued on `stream`; the call returns without synchronising
