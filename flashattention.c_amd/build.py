@@ -8,6 +8,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
 
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
+``libflashattn_amd_kv.so`` (the KV-cache attention extension, include/flashattn_amd_kv.h; ``KV_SOURCES``) is always built beside it.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
 They are NOT part of the product library: its ``fa_forward_ex`` rejects their variant numbers.
@@ -55,9 +56,14 @@ ABLATION_SOURCES = ["experiments/" + f for f in (
 ABLATION_DEPENDENT = ["fa_fwd_bf16.hip", "fa_fwd_bf16_x4.hip", "fa_fwd_bf16_pipelined.hip", "fa_fwd_bf16_x2.hip", "fa_plan.cpp", "fa_counters.cpp", "fa_launch.cpp", "fa_api.cpp",
                       "fa_split_f32_d32.hip", "fa_split_f32_d64.hip"]
 ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
+# libflashattn_amd_kv.so, the KV-cache attention extension behind include/flashattn_amd_kv.h: a library of its own (ABI 6 of the product
+# library is frozen), self-contained -- it shares headers with the product, no object.  Longest translation unit first.
+KV_SOURCES = ["fa_kv_decode.hip", "fa_kv_combine.hip", "fa_kv_plan.cpp"]
+KV_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv.so")
 ABL_DRIVER_PATH = os.path.join(PKG_DIR, "fa_driver_ablation")
 # every header under csrc/ (globbed: a new header cannot be forgotten -- ADVICE r04) plus the C ABI
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [os.path.join(ROOT, "include", "flashattn_amd.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [os.path.join(ROOT, "include", "flashattn_amd.h"),
+                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kv.h")]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
                 "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 # per-source extras.  The split kernel keeps its fp32 arithmetic scalar: the SLP vectoriser would pair it into
@@ -117,12 +123,16 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
+        # one pool for both libraries; the KV decode kernels are among the longest translation units, so they start first
+        kv_futs = [ex.submit(_compile, s, force) for s in KV_SOURCES]
         objs = list(ex.map(lambda s: _compile(s, force), LIB_SOURCES))
+        kv_objs = [f.result() for f in kv_futs]
         abl_objs = []
         if ablation:
             abl_objs = list(ex.map(lambda s: _compile(s, force, True), ABLATION_SOURCES + ABLATION_DEPENDENT))
             abl_objs += [o for s_, o in zip(LIB_SOURCES, objs) if s_ not in ABLATION_DEPENDENT]
     _link(LIB_PATH, objs, force)
+    _link(KV_LIB_PATH, kv_objs, force)
     _build_driver(DRIVER_PATH, LIB_PATH, "flashattn_amd", force)
     if ablation:
         _link(ABL_LIB_PATH, abl_objs, force)
@@ -130,8 +140,34 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
     if torch_binding:
         build_torch_binding(force=force, verbose=verbose)
     if verbose:
-        print(f"built {LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
+        print(f"built {LIB_PATH} and {KV_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
     return LIB_PATH
+
+
+# the measurement switches of the KV-cache sources and the translation units that read them
+KV_DEFINE_USERS = {"FA_KV_TARGET_WGS": ["fa_kv_plan.cpp"], "FA_KV_MIN_SHARE": ["fa_kv_plan.cpp"], "FA_KV_P_TERMS": ["fa_kv_decode.hip"]}
+
+
+def build_kv_variant(tag: str, defines, outdir: str) -> str:
+    """Measurement builds of the KV-cache library (profiles/kv_decode.py): the sources that read one of `defines` (e.g. "FA_KV_TARGET_WGS=1024",
+    "FA_KV_P_TERMS=1") recompiled with them, linked with the product objects of the rest into ``outdir/libflashattn_amd_kv_<tag>.so``.
+    Never loaded by the package."""
+    build(force=False)
+    os.makedirs(outdir, exist_ok=True)
+    objs = []
+    for src in KV_SOURCES:
+        obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+        mine = [d for d in defines if src in KV_DEFINE_USERS[d.split("=")[0]]]
+        if mine:
+            obj = os.path.join(outdir, os.path.splitext(src)[0] + f".{tag}.o")
+            cmd = [hipcc(), *COMMON_FLAGS, "-DFA_ABLATION=0", *[f"-D{d}" for d in mine], "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed on {src} ({tag}):\n{r.stdout}\n{r.stderr}")
+        objs.append(obj)
+    out = os.path.join(outdir, f"libflashattn_amd_kv_{tag}.so")
+    _link(out, objs, True)
+    return out
 
 
 ASAN_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_asan.so")

@@ -23,9 +23,10 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _cabi
+from . import _cabi, _cabi_kv
 
-__all__ = ["forward", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "stats", "SUPPORTED_HEAD_DIMS"]
+__all__ = ["forward", "forward_kv", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv", "stats",
+           "SUPPORTED_HEAD_DIMS", "KV_HEAD_DIMS"]
 
 SUPPORTED_HEAD_DIMS = (32, 64, 128)   # ... by every kernel family; ``kernel="auto"`` takes any head dim up to MAX_HEAD_DIM
 MAX_HEAD_DIM = 256
@@ -132,6 +133,88 @@ def workspace_bytes(bh: int, n: int, d: int, causal: bool = False, *, dtype: tor
     if out_dtype is not None and out_dtype != dtype:
         dt = _cabi.FA_DTYPE_BF16_OUT_F32
     return int(_cabi.lib().fa_workspace_bytes(int(bh), int(n), int(d), int(bool(causal)), dt, _kernel_id(kernel)))
+
+
+KV_HEAD_DIMS = (64, 128)
+
+
+def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
+               kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None,
+               out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+    """Attention of few query rows against a K/V cache (``include/flashattn_amd_kv.h``): decode, chunked prefill, cross-attention, GQA.
+
+    ``q`` is ``(BHq, nq, d)``; ``k``, ``v`` are ``(BHkv, capacity, d)`` caches of which the first ``kv_len`` rows (default: all ``capacity``)
+    are attended to; ``BHq = BHkv * group``, query slab ``s`` reads K/V slab ``s // group``.  ``kv_lens``, an int32 tensor ``(BHkv,)`` on the
+    device, gives each slab its own length (clamped to ``[0, kv_len]``); it is read by the kernel, never by the host, so a captured graph can
+    be replayed while the cache grows.  ``causal`` is bottom-right aligned: query row ``i`` sees keys ``j <= len - nq + i``.  Rows without a
+    visible key get ``O = 0``, ``LSE = -inf``.  bfloat16 tensors, ``d`` 64 or 128; ``out_dtype=torch.float32`` stores the fp32 accumulator.
+    Arithmetic and accuracy are those of ``forward(..., out_dtype=torch.float32)`` on bf16 tensors (P as two bf16 terms) for both outputs.
+    Scratch (``workspace_bytes_kv``; key-split launches only) comes from ``torch.empty`` unless ``workspace`` passes a ``torch.uint8`` tensor.
+    """
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be 3-D (batch*heads, rows, head_dim), got shape {tuple(t.shape)}")
+    if k.shape != v.shape:
+        raise ValueError(f"k and v must have identical shapes, got {tuple(k.shape)}, {tuple(v.shape)}")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("q, k, v must share one dtype")
+    if q.dtype != torch.bfloat16:
+        raise TypeError(f"dtype {q.dtype} not supported by forward_kv (bfloat16: caches are 16-bit)")
+    if not (q.is_cuda and k.is_cuda and v.is_cuda) or not (q.device == k.device == v.device):
+        raise ValueError("q, k, v must live on the same GPU (there is no CPU implementation of this operator)")
+    bhq, nq, d = q.shape
+    bhkv, capacity, dk = k.shape
+    if dk != d:
+        raise ValueError(f"head_dim of q ({d}) and of k, v ({dk}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by forward_kv (choose from {KV_HEAD_DIMS})")
+    if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
+        raise ValueError("empty batch or sequence")
+    if bhq % bhkv != 0:
+        raise ValueError(f"q has {bhq} slabs, k / v have {bhkv}: not a whole number of query heads per K/V head")
+    group = bhq // bhkv
+    nk = capacity if kv_len is None else int(kv_len)
+    if not 1 <= nk <= capacity:
+        raise ValueError(f"kv_len {nk} outside 1 .. capacity = {capacity}")
+    if kv_lens is not None:
+        if not isinstance(kv_lens, torch.Tensor):
+            raise TypeError("kv_lens must be a torch.Tensor")
+        if kv_lens.dtype != torch.int32 or kv_lens.shape != (bhkv,) or kv_lens.device != q.device or not kv_lens.is_contiguous():
+            raise ValueError(f"kv_lens must be a contiguous torch.int32 tensor of shape ({bhkv},) on {q.device}")
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
+    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
+    lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
+    L = _cabi_kv.lib()
+    with torch.cuda.device(q.device):
+        need = int(L.fa_kv_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
+        elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
+            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = L.fa_kv_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                             bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
+                             d, float(scale), int(bool(causal)), dt,
+                             workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                             workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+    _cabi_kv.check(rc)
+    return (out, lse) if return_lse else out
+
+
+def workspace_bytes_kv(bh_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *, out_dtype: torch.dtype = torch.bfloat16) -> int:
+    """Bytes of scratch ``forward_kv`` can use for these shapes (``fa_kv_workspace_bytes``); 0 when the plan does not split the keys."""
+    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    return int(_cabi_kv.lib().fa_kv_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:
