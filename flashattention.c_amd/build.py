@@ -9,6 +9,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
 ``libflashattn_amd_kv.so`` (the KV-cache attention extension, include/flashattn_amd_kv.h; ``KV_SOURCES``) is always built beside it.
+``libflashattn_amd_paged.so`` (paged KV-cache attention, include/flashattn_amd_paged.h; ``PAGED_SOURCES``) likewise.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
 They are NOT part of the product library: its ``fa_forward_ex`` rejects their variant numbers.
@@ -60,10 +61,15 @@ ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
 # library is frozen), self-contained -- it shares headers with the product, no object.  Longest translation unit first.
 KV_SOURCES = ["fa_kv_decode.hip", "fa_kv_combine.hip", "fa_kv_plan.cpp"]
 KV_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv.so")
+# libflashattn_amd_paged.so, the paged twin behind include/flashattn_amd_paged.h: its own decode kernel and host side, and the OBJECT of the KV library's
+# merge kernel (fa_kv_combine.hip is compiled once).  It exports no fa_kv_* symbol: the plan it shares is inline in csrc/fa_kv.h.
+PAGED_SOURCES = ["fa_paged_decode.hip", "fa_kv_combine.hip", "fa_paged_host.cpp"]
+PAGED_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_paged.so")
 ABL_DRIVER_PATH = os.path.join(PKG_DIR, "fa_driver_ablation")
 # every header under csrc/ (globbed: a new header cannot be forgotten -- ADVICE r04) plus the C ABI
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [os.path.join(ROOT, "include", "flashattn_amd.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kv.h")]
+                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kv.h"),
+                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_paged.h")]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
                 "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 # per-source extras.  The split kernel keeps its fp32 arithmetic scalar: the SLP vectoriser would pair it into
@@ -123,16 +129,19 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        # one pool for both libraries; the KV decode kernels are among the longest translation units, so they start first
+        # one pool for all three libraries; the decode kernels are among the longest translation units, so they start first
+        paged_futs = {s: ex.submit(_compile, s, force) for s in PAGED_SOURCES if s not in KV_SOURCES}
         kv_futs = [ex.submit(_compile, s, force) for s in KV_SOURCES]
         objs = list(ex.map(lambda s: _compile(s, force), LIB_SOURCES))
         kv_objs = [f.result() for f in kv_futs]
+        paged_objs = [paged_futs[s].result() if s in paged_futs else kv_objs[KV_SOURCES.index(s)] for s in PAGED_SOURCES]
         abl_objs = []
         if ablation:
             abl_objs = list(ex.map(lambda s: _compile(s, force, True), ABLATION_SOURCES + ABLATION_DEPENDENT))
             abl_objs += [o for s_, o in zip(LIB_SOURCES, objs) if s_ not in ABLATION_DEPENDENT]
     _link(LIB_PATH, objs, force)
     _link(KV_LIB_PATH, kv_objs, force)
+    _link(PAGED_LIB_PATH, paged_objs, force)
     _build_driver(DRIVER_PATH, LIB_PATH, "flashattn_amd", force)
     if ablation:
         _link(ABL_LIB_PATH, abl_objs, force)
@@ -140,7 +149,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
     if torch_binding:
         build_torch_binding(force=force, verbose=verbose)
     if verbose:
-        print(f"built {LIB_PATH} and {KV_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
+        print(f"built {LIB_PATH}, {KV_LIB_PATH} and {PAGED_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
     return LIB_PATH
 
 

@@ -28,9 +28,39 @@ struct KvPlan {
     int32_t share;       // keys per share, a multiple of 64
 };
 
-// bh_kv, group, nq, nk as validated by the caller (all >= 1)
-KvPlan kv_plan(int64_t bh_kv, int32_t group, int64_t nq, int64_t nk);
-size_t kv_workspace_bytes(const KvPlan& pl, int64_t bh_kv, int32_t group, int64_t nq, int32_t d);
+// bh_kv, group, nq, nk as validated by the caller (all >= 1).  Inline: libflashattn_amd_paged.so (fa_paged_host.cpp) plans with the same code and
+// links no host object of this library.
+// The M = group * nq rows of a K/V slab are packed into T tiles of kKvRowTile rows; a launch has bh_kv * T * S workgroups.
+//   S = clamp(ceil(target / (bh_kv * T)), 1, min(64, nk / min_share)), share = ceil(nk / S) rounded up to 64 keys,
+//   S is lowered (and the share recomputed) until the last share is not empty.
+inline KvPlan kv_plan(int64_t bh_kv, int32_t group, int64_t nq, int64_t nk)
+{
+    KvPlan pl;
+    const int64_t m = (int64_t)group * nq;
+    const int64_t tiles = (m + kKvRowTile - 1) / kKvRowTile;
+    pl.row_tiles = (int32_t)tiles;
+    const int64_t wgs = bh_kv * tiles;
+    int64_t s = (kKvTargetWorkgroups + wgs - 1) / wgs;
+    int64_t cap = nk / kKvMinShareKeys;
+    if (cap > kKvMaxSplits) cap = kKvMaxSplits;
+    if (s > cap) s = cap;
+    if (s < 1) s = 1;
+    int64_t share;
+    for (;;) {   // the largest S <= s whose last share is not empty, with the share size that belongs to it
+        share = ((nk + s - 1) / s + 63) / 64 * 64;
+        if (s > 1 && (s - 1) * share >= nk) --s; else break;
+    }
+    pl.splits = (int32_t)s;
+    pl.share = (int32_t)share;
+    return pl;
+}
+
+inline size_t kv_workspace_bytes(const KvPlan& pl, int64_t bh_kv, int32_t group, int64_t nq, int32_t d)
+{
+    if (pl.splits <= 1) return 0;
+    const size_t rows = (size_t)bh_kv * (size_t)group * (size_t)nq;
+    return ((size_t)pl.splits * rows * (size_t)(d + 1) * 4 + 255) / 256 * 256;
+}
 
 struct KvParams {
     const void* q;          // (bh_kv * group, nq, d) bf16: the M = group * nq rows of one K/V slab are contiguous ("packed rows")

@@ -10,38 +10,6 @@
 
 namespace fa {
 
-// The M = group * nq rows of a K/V slab are packed into T tiles of kKvRowTile rows; a launch has bh_kv * T * S workgroups.
-//   S = clamp(ceil(target / (bh_kv * T)), 1, min(64, nk / min_share)), share = ceil(nk / S) rounded up to 64 keys,
-//   S is lowered (and the share recomputed) until the last share is not empty.
-KvPlan kv_plan(int64_t bh_kv, int32_t group, int64_t nq, int64_t nk)
-{
-    KvPlan pl;
-    const int64_t m = (int64_t)group * nq;
-    const int64_t tiles = (m + kKvRowTile - 1) / kKvRowTile;
-    pl.row_tiles = (int32_t)tiles;
-    const int64_t wgs = bh_kv * tiles;
-    int64_t s = (kKvTargetWorkgroups + wgs - 1) / wgs;
-    int64_t cap = nk / kKvMinShareKeys;
-    if (cap > kKvMaxSplits) cap = kKvMaxSplits;
-    if (s > cap) s = cap;
-    if (s < 1) s = 1;
-    int64_t share;
-    for (;;) {   // the largest S <= s whose last share is not empty, with the share size that belongs to it
-        share = ((nk + s - 1) / s + 63) / 64 * 64;
-        if (s > 1 && (s - 1) * share >= nk) --s; else break;
-    }
-    pl.splits = (int32_t)s;
-    pl.share = (int32_t)share;
-    return pl;
-}
-
-size_t kv_workspace_bytes(const KvPlan& pl, int64_t bh_kv, int32_t group, int64_t nq, int32_t d)
-{
-    if (pl.splits <= 1) return 0;
-    const size_t rows = (size_t)bh_kv * (size_t)group * (size_t)nq;
-    return ((size_t)pl.splits * rows * (size_t)(d + 1) * 4 + 255) / 256 * 256;
-}
-
 static thread_local char g_kv_error[320] = "";
 
 static int kv_fail(int code, const char* fmt, ...)

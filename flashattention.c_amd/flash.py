@@ -23,9 +23,10 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv
+from . import _cabi, _cabi_kv, _cabi_paged
 
-__all__ = ["forward", "forward_kv", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv", "stats",
+__all__ = ["forward", "forward_kv", "forward_paged", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
+           "workspace_bytes_paged", "stats",
            "SUPPORTED_HEAD_DIMS", "KV_HEAD_DIMS"]
 
 SUPPORTED_HEAD_DIMS = (32, 64, 128)   # ... by every kernel family; ``kernel="auto"`` takes any head dim up to MAX_HEAD_DIM
@@ -215,6 +216,101 @@ def workspace_bytes_kv(bh_kv: int, group: int, nq: int, nk: int, d: int, causal:
     """Bytes of scratch ``forward_kv`` can use for these shapes (``fa_kv_workspace_bytes``); 0 when the plan does not split the keys."""
     dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
     return int(_cabi_kv.lib().fa_kv_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
+
+
+def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
+                  seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None, scale: float = 1.0, return_lse: bool = False,
+                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+    """``forward_kv`` over a paged cache (``include/flashattn_amd_paged.h``): K/V rows live in pages of a shared pool, found through a block table.
+
+    ``k_pool``, ``v_pool`` are ``(pages, page, d)`` (one K/V head) or ``(pages, page, H, d)``; their strides are taken as they are, so a
+    ``(pages, H, page, d).permute(0, 2, 1, 3)`` view works without a copy -- a pool is never copied: a last stride other than 1 or a stride that
+    is not a multiple of 8 elements raises.  ``block_table`` is int32 ``(batch, max_pages)`` on the device: entry ``p`` of sequence ``b`` is the
+    physical page of its rows ``[p * page, (p + 1) * page)``.  ``q`` is ``(batch * H * group, nq, d)``; query slab ``((b * H) + h) * group + g``
+    reads head ``h`` of sequence ``b``.  ``kv_len`` (default ``max_pages * page``) bounds every sequence; ``seq_lens``, int32 ``(batch,)`` on the
+    device, gives each its own length (clamped to ``[0, kv_len]``).  Table and lengths are read by the kernel only, so one captured graph
+    follows a cache that grows and whose pages move.  Pages of 16 .. 65536 rows, a power of two.  Everything else -- ``causal``, rows without
+    keys, dtypes, arithmetic, scratch (``workspace_bytes_paged``) -- is ``forward_kv``'s, and so is the result, bit for bit, on the gathered cache.
+    """
+    for name, t in (("q", q), ("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if q.dim() != 3:
+        raise ValueError(f"q must be 3-D (batch*heads, rows, head_dim), got shape {tuple(q.shape)}")
+    if k_pool.dim() not in (3, 4):
+        raise ValueError(f"k_pool must be (pages, page, d) or (pages, page, H, d), got shape {tuple(k_pool.shape)}")
+    if k_pool.shape != v_pool.shape or k_pool.stride() != v_pool.stride():
+        raise ValueError(f"k_pool and v_pool must have identical shapes and strides, got {tuple(k_pool.shape)} / {k_pool.stride()} and "
+                         f"{tuple(v_pool.shape)} / {v_pool.stride()}")
+    if not (q.dtype == k_pool.dtype == v_pool.dtype):
+        raise TypeError("q, k_pool, v_pool must share one dtype")
+    if q.dtype != torch.bfloat16:
+        raise TypeError(f"dtype {q.dtype} not supported by forward_paged (bfloat16: caches are 16-bit)")
+    if not (q.is_cuda and k_pool.is_cuda and v_pool.is_cuda and block_table.is_cuda) or not (q.device == k_pool.device == v_pool.device == block_table.device):
+        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
+    bhq, nq, d = q.shape
+    pages, page = k_pool.shape[0], k_pool.shape[1]
+    heads_kv = k_pool.shape[2] if k_pool.dim() == 4 else 1
+    if k_pool.shape[-1] != d:
+        raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool.shape[-1]}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by forward_paged (choose from {KV_HEAD_DIMS})")
+    if k_pool.stride(-1) != 1:
+        raise ValueError(f"the pools' last stride must be 1, got {k_pool.stride(-1)} (a pool is never copied)")
+    page_stride, row_stride = k_pool.stride(0), k_pool.stride(1)
+    head_stride = k_pool.stride(2) if k_pool.dim() == 4 else 0
+    if page_stride % 8 or row_stride % 8 or head_stride % 8:
+        raise ValueError(f"pool strides must be multiples of 8 elements (16 bytes), got {k_pool.stride()} (a pool is never copied)")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous():
+        raise ValueError("block_table must be a contiguous torch.int32 tensor of shape (batch, max_pages)")
+    batch, max_pages = block_table.shape
+    if bhq < 1 or nq < 1 or batch < 1 or max_pages < 1 or pages < 1 or heads_kv < 1:
+        raise ValueError("empty batch, sequence, pool or block table")
+    if bhq % (batch * heads_kv) != 0:
+        raise ValueError(f"q has {bhq} slabs, the cache {batch} sequences x {heads_kv} heads: not a whole number of query heads per K/V head")
+    group = bhq // (batch * heads_kv)
+    nk = max_pages * page if kv_len is None else int(kv_len)
+    if not 1 <= nk <= max_pages * page:
+        raise ValueError(f"kv_len {nk} outside 1 .. max_pages * page = {max_pages * page}")
+    if seq_lens is not None:
+        if not isinstance(seq_lens, torch.Tensor):
+            raise TypeError("seq_lens must be a torch.Tensor")
+        if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch,) or seq_lens.device != q.device or not seq_lens.is_contiguous():
+            raise ValueError(f"seq_lens must be a contiguous torch.int32 tensor of shape ({batch},) on {q.device}")
+    q = q.contiguous()
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
+    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
+    lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
+    cache = _cabi_paged.FaPagedCache(k_pool.data_ptr(), v_pool.data_ptr(), pages, page, page_stride, row_stride, head_stride,
+                                     block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
+    L = _cabi_paged.lib()
+    with torch.cuda.device(q.device):
+        need = int(L.fa_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
+        elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
+            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = L.fa_paged_forward(q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                                batch, heads_kv, group, nq, nk, d, float(scale), int(bool(causal)), dt,
+                                workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+    _cabi_paged.check(rc)
+    return (out, lse) if return_lse else out
+
+
+def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *,
+                          out_dtype: torch.dtype = torch.bfloat16) -> int:
+    """Bytes of scratch ``forward_paged`` can use for these shapes (``fa_paged_workspace_bytes`` = ``workspace_bytes_kv`` at ``batch * heads_kv``)."""
+    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    return int(_cabi_paged.lib().fa_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:
