@@ -23,9 +23,9 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_paged
 
-__all__ = ["forward", "forward_kv", "forward_paged", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
+__all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
            "SUPPORTED_HEAD_DIMS", "KV_HEAD_DIMS"]
 
@@ -311,6 +311,165 @@ def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: in
     """Bytes of scratch ``forward_paged`` can use for these shapes (``fa_paged_workspace_bytes`` = ``workspace_bytes_kv`` at ``batch * heads_kv``)."""
     dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
     return int(_cabi_paged.lib().fa_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
+
+
+def _check_fp8_cache(fn: str, q: torch.Tensor, named) -> None:
+    """dtype and device checks the two fp8 entries share: bf16 q, e4m3fn caches on q's GPU."""
+    for name, t in named:
+        if t.dtype == torch.uint8:
+            raise TypeError(f"{name} is torch.uint8: {fn} takes torch.float8_e4m3fn -- reinterpret the bytes with {name}.view(torch.float8_e4m3fn)")
+        if t.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"dtype {t.dtype} of {name} not supported by {fn} (torch.float8_e4m3fn)")
+    if q.dtype != torch.bfloat16:
+        raise TypeError(f"dtype {q.dtype} of q not supported by {fn} (bfloat16)")
+    if not q.is_cuda or any(not t.is_cuda or t.device != q.device for _, t in named):
+        raise ValueError("q and the cache must live on the same GPU (there is no CPU implementation of this operator)")
+
+
+def _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need):
+    """out, lse and workspace as forward_kv / forward_paged prepare them"""
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
+    lse = torch.empty(q.shape[:2], dtype=torch.float32, device=q.device) if return_lse else None
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
+    elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
+    return out, lse, workspace
+
+
+def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
+                   kv_len: Optional[int] = None, kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False,
+                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+    """``forward_kv`` over a cache of 8-bit floats (``include/flashattn_amd_kv8.h``): half the K/V bytes of a call.
+
+    ``q`` is bfloat16 ``(BHq, nq, d)``; ``k8``, ``v8`` are ``torch.float8_e4m3fn`` ``(BHkv, capacity, d)`` (a ``torch.uint8`` tensor is rejected:
+    ``.view(torch.float8_e4m3fn)`` it).  Logical K = ``k_scale`` x the stored values, logical V = ``v_scale`` x them: one positive float per
+    tensor and call.  The kernel dequantises to bf16 exactly and runs the arithmetic of ``forward_kv``; ``k_scale`` is folded into ``scale`` as
+    one fp32 product, ``v_scale`` multiplies the normalised result once, the LSE is that of the scaled scores.  With ``v_scale`` a power of two
+    the result is bit for bit ``v_scale * forward_kv(q, k8.to(bfloat16), v8.to(bfloat16), scale=fp32(scale * k_scale))``.  Everything else --
+    ``kv_len``, ``kv_lens``, ``causal``, rows without keys, ``d``, output dtypes -- is ``forward_kv``'s; scratch has the size ``workspace_bytes_kv``
+    gives for the same shapes.
+    """
+    for name, t in (("q", q), ("k8", k8), ("v8", v8)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be 3-D (batch*heads, rows, head_dim), got shape {tuple(t.shape)}")
+    if k8.shape != v8.shape:
+        raise ValueError(f"k8 and v8 must have identical shapes, got {tuple(k8.shape)}, {tuple(v8.shape)}")
+    _check_fp8_cache("forward_kv_fp8", q, (("k8", k8), ("v8", v8)))
+    bhq, nq, d = q.shape
+    bhkv, capacity, dk = k8.shape
+    if dk != d:
+        raise ValueError(f"head_dim of q ({d}) and of k8, v8 ({dk}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by forward_kv_fp8 (choose from {KV_HEAD_DIMS})")
+    if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
+        raise ValueError("empty batch or sequence")
+    if bhq % bhkv != 0:
+        raise ValueError(f"q has {bhq} slabs, k8 / v8 have {bhkv}: not a whole number of query heads per K/V head")
+    group = bhq // bhkv
+    nk = capacity if kv_len is None else int(kv_len)
+    if not 1 <= nk <= capacity:
+        raise ValueError(f"kv_len {nk} outside 1 .. capacity = {capacity}")
+    if kv_lens is not None:
+        if not isinstance(kv_lens, torch.Tensor):
+            raise TypeError("kv_lens must be a torch.Tensor")
+        if kv_lens.dtype != torch.int32 or kv_lens.shape != (bhkv,) or kv_lens.device != q.device or not kv_lens.is_contiguous():
+            raise ValueError(f"kv_lens must be a contiguous torch.int32 tensor of shape ({bhkv},) on {q.device}")
+    q, k8, v8 = q.contiguous(), k8.contiguous(), v8.contiguous()
+    L = _cabi_kv8.lib()
+    with torch.cuda.device(q.device):
+        odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
+        dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
+        need = int(L.fa_kv8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = L.fa_kv8_forward(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                              bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
+                              d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt,
+                              workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                              workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+    _cabi_kv8.check(rc)
+    return (out, lse) if return_lse else out
+
+
+def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
+                      k_scale: float = 1.0, v_scale: float = 1.0, seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None,
+                      scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                      workspace: Optional[torch.Tensor] = None):
+    """``forward_paged`` over pools of 8-bit floats (``include/flashattn_amd_kv8.h``); scales and arithmetic as in ``forward_kv_fp8``.
+
+    ``k_pool8``, ``v_pool8`` are ``torch.float8_e4m3fn`` ``(pages, page, d)`` or ``(pages, page, H, d)`` (``torch.uint8`` is rejected: ``.view`` it).
+    Their strides are taken as they are and a pool is never copied: a last stride other than 1 or a stride that is not a multiple of 16
+    elements (16 bytes) raises.  Block table, ``seq_lens``, ``kv_len``, page sizes and everything else are ``forward_paged``'s, and the result is
+    ``forward_kv_fp8``'s, bit for bit, on the gathered bytes; scratch has the size ``workspace_bytes_paged`` gives for the same shapes.
+    """
+    for name, t in (("q", q), ("k_pool8", k_pool8), ("v_pool8", v_pool8), ("block_table", block_table)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if q.dim() != 3:
+        raise ValueError(f"q must be 3-D (batch*heads, rows, head_dim), got shape {tuple(q.shape)}")
+    if k_pool8.dim() not in (3, 4):
+        raise ValueError(f"k_pool8 must be (pages, page, d) or (pages, page, H, d), got shape {tuple(k_pool8.shape)}")
+    if k_pool8.shape != v_pool8.shape or k_pool8.stride() != v_pool8.stride():
+        raise ValueError(f"k_pool8 and v_pool8 must have identical shapes and strides, got {tuple(k_pool8.shape)} / {k_pool8.stride()} and "
+                         f"{tuple(v_pool8.shape)} / {v_pool8.stride()}")
+    _check_fp8_cache("forward_paged_fp8", q, (("k_pool8", k_pool8), ("v_pool8", v_pool8)))
+    if not block_table.is_cuda or block_table.device != q.device:
+        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
+    bhq, nq, d = q.shape
+    pages, page = k_pool8.shape[0], k_pool8.shape[1]
+    heads_kv = k_pool8.shape[2] if k_pool8.dim() == 4 else 1
+    if k_pool8.shape[-1] != d:
+        raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool8.shape[-1]}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by forward_paged_fp8 (choose from {KV_HEAD_DIMS})")
+    if k_pool8.stride(-1) != 1:
+        raise ValueError(f"the pools' last stride must be 1, got {k_pool8.stride(-1)} (a pool is never copied)")
+    page_stride, row_stride = k_pool8.stride(0), k_pool8.stride(1)
+    head_stride = k_pool8.stride(2) if k_pool8.dim() == 4 else 0
+    if page_stride % 16 or row_stride % 16 or head_stride % 16:
+        raise ValueError(f"pool strides must be multiples of 16 elements (16 bytes), got {k_pool8.stride()} (a pool is never copied)")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous():
+        raise ValueError("block_table must be a contiguous torch.int32 tensor of shape (batch, max_pages)")
+    batch, max_pages = block_table.shape
+    if bhq < 1 or nq < 1 or batch < 1 or max_pages < 1 or pages < 1 or heads_kv < 1:
+        raise ValueError("empty batch, sequence, pool or block table")
+    if bhq % (batch * heads_kv) != 0:
+        raise ValueError(f"q has {bhq} slabs, the cache {batch} sequences x {heads_kv} heads: not a whole number of query heads per K/V head")
+    group = bhq // (batch * heads_kv)
+    nk = max_pages * page if kv_len is None else int(kv_len)
+    if not 1 <= nk <= max_pages * page:
+        raise ValueError(f"kv_len {nk} outside 1 .. max_pages * page = {max_pages * page}")
+    if seq_lens is not None:
+        if not isinstance(seq_lens, torch.Tensor):
+            raise TypeError("seq_lens must be a torch.Tensor")
+        if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch,) or seq_lens.device != q.device or not seq_lens.is_contiguous():
+            raise ValueError(f"seq_lens must be a contiguous torch.int32 tensor of shape ({batch},) on {q.device}")
+    q = q.contiguous()
+    cache = _cabi_kv8.FaPagedCache(k_pool8.data_ptr(), v_pool8.data_ptr(), pages, page, page_stride, row_stride, head_stride,
+                                   block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
+    L = _cabi_kv8.lib()
+    with torch.cuda.device(q.device):
+        odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
+        dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
+        need = int(L.fa_kv8_workspace_bytes(batch * heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = L.fa_kv8_paged_forward(q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                                    batch, heads_kv, group, nq, nk, d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt,
+                                    workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                                    workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+    _cabi_kv8.check(rc)
+    return (out, lse) if return_lse else out
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:
