@@ -28,8 +28,8 @@ struct KvPlan {
     int32_t share;       // keys per share, a multiple of 64
 };
 
-// bh_kv, group, nq, nk as validated by the caller (all >= 1).  Inline: libflashattn_amd_paged.so (fa_paged_host.cpp) plans with the same code and
-// links no host object of this library.
+// bh_kv, group, nq, nk as validated by the caller (all >= 1).  Inline: the paged and the fp8 library plan with the same code (fa_kv_host.h)
+// and link no host object of this library.
 // The M = group * nq rows of a K/V slab are packed into T tiles of kKvRowTile rows; a launch has bh_kv * T * S workgroups.
 //   S = clamp(ceil(target / (bh_kv * T)), 1, min(64, nk / min_share)), share = ceil(nk / S) rounded up to 64 keys,
 //   S is lowered (and the share recomputed) until the last share is not empty.

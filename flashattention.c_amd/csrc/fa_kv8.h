@@ -1,6 +1,6 @@
 // fa_kv8.h -- what the translation units of libflashattn_amd_kv8.so share (include/flashattn_amd_kv8.h is the boundary).  The library is the
 // KV-cache forward of fa_kv.h / fa_paged.h over a cache of 8-bit floats (OCP e4m3fn): the plan (kv_plan) and the launch parameters are
-// theirs; the decode kernel and the merge kernel (fa_kv_combine.hip's plus the multiplication by v_scale) are its own.  It links no object of
+// theirs; the decode kernel and the merge kernel (fa_kv_combine_kernel.h's body with the multiplication by v_scale) are its own.  It links no object of
 // the other libraries.
 #pragma once
 #include "fa_paged.h"

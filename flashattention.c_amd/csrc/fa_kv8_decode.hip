@@ -1,16 +1,13 @@
-// fa_kv8_decode.hip -- fa_kv_decode.hip and fa_paged_decode.hip over a cache of 8-bit floats (OCP e4m3fn, one byte per element): the same
-// workgroup, loop, masking, merge and epilogue, as ONE template over <D, CAUSAL, OUT_F32, PAGED> (the two 16-bit files differ only in how a
-// row's address is formed; they are left untouched: their device code is pinned).  No counterpart in the reference.
+// fa_kv8_decode.hip -- the decode kernel of libflashattn_amd_kv8.so: fa_kv_decode_core.h's workgroup, arithmetic, merge and page walk over a
+// cache of 8-bit floats (OCP e4m3fn, one byte per element), contiguous or paged, with a loop of its own.  No counterpart in the reference.
 //
 // Arithmetic -- the contract of include/flashattn_amd_kv8.h.  e4m3 -> bf16 is exact for every non-NaN code, so K and V are dequantised to
-// bf16 WITHOUT their scales and then meet the very instruction sequence of the 16-bit kernels: one bf16 product for Q.K^T into fp32, P as
-// bf16 hi + bf16 lo, the row sum on the matrix pipe against the all-ones operand, the same contraction order over d and over keys, the same
-// four-wave merge.  k_scale arrives folded into the softmax scale (host, one fp32 product); v_scale multiplies the normalised fp32 result
-// once: here, before the store to o, in an unsplit launch; in fa_kv8_combine.hip, behind the merge of the shares, in a split one (that file
-// says why the partial outputs stay unscaled).  With v_scale a power of two the result is, bit for bit, v_scale x what the 16-bit kernels give
-// on the cache dequantised to bf16.
+// bf16 WITHOUT their scales and then meet the very instruction sequence of the 16-bit kernels.  k_scale arrives folded into the softmax scale
+// (host, one fp32 product); v_scale multiplies the normalised fp32 result once: here, before the store to o, in an unsplit launch; in
+// fa_kv8_combine.hip, behind the merge of the shares, in a split one.  With v_scale a power of two the result is, bit for bit, v_scale x what
+// the 16-bit kernels give on the cache dequantised to bf16.
 //
-// Data movement, per wave and 64-key block -- what is new:
+// Data movement, per wave and 64-key block -- what differs from fa_kv_decode16_body.h:
 //   K  the A operand of K Q^T is "lane (key, half) holds 8 consecutive columns of its key per 16-column step": one 8-byte load at
 //      ks * 16 + hi * 8 (the 16-bit kernels: one 16-byte load).  The bytes stay in registers as they came and are converted
 //      (v_cvt_pk_f32_fp8, then the pack to bf16) in front of the matrix instruction that takes them.
@@ -22,18 +19,12 @@
 // Every load is a register load: the compiler counts vmcnt itself.  The look-ahead is kept -- the bytes of block j + 1 (K and V, registers)
 // are in flight while block j is computed -- and the image is written and read by the same wave inside one step (LDS operations of a wave
 // execute in order), so one image per wave suffices: half the LDS of the 16-bit kernels and no barrier in the loop.
-// Keys at or beyond the length (or the share's end, or above a row's causal diagonal) are masked to -inf before the maximum; their loads are
-// redirected to the last valid row of the share, so no row >= len is ever read.
-// Paged: table reads as in fa_paged_decode.hip -- wave-uniform, through the constant address space, issued at the end of a step and first
-// used two steps later; the redirect acts on the logical row, before the lookup, so no entry at or beyond ceil(len / page) is ever read.
 #include "fa_kv8.h"
-#include "fa_bf16_common.h"
+#include "fa_kv_decode_core.h"
 
 namespace fa {
 
-typedef __attribute__((address_space(4))) const int32_t cst_i32_t;   // a load through it is a scalar load wherever its address is uniform
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-static_assert(kPagedBlockPages * kPagedMinPage == kKvBlk, "the entries of one block");
 
 template <int D>
 struct Kv8Cfg {
@@ -42,8 +33,7 @@ struct Kv8Cfg {
     static constexpr int kVLoads = kKvBlk * D / 1024;      // 16-byte V loads per lane and block
     static constexpr int kRowsPerLoad = kWave / LPR;       // keys one V load instruction covers
     static constexpr int kVTile = kKvBlk * 2 * D;          // bytes of the V image (64 keys, bf16)
-    static constexpr int kMergeStride = D + 4;             // floats per row of a wave's O in the merge (padded against bank conflicts)
-    static constexpr int kMergeBytes = kKvRowTile * kMergeStride * 4;
+    static constexpr int kMergeBytes = kKvRowTile * kKvMergeStride(D) * 4;
     static constexpr int kWaveLds = kVTile > kMergeBytes ? kVTile : kMergeBytes;   // one image per wave, reused by the merge
     static_assert(kPagedMinPage % kRowsPerLoad == 0, "a V load must not straddle a 16-key group");
     static_assert(kWaveLds % 128 == 0, "sub-tile alignment");
@@ -85,49 +75,18 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lq = lane & 31, hi = lane >> 5;
 
-    // share fastest: the shares of a row tile run side by side
-    const int s_idx = blockIdx.x % p.splits;
-    const int tile = (blockIdx.x / p.splits) % p.row_tiles;
-    const int slab = blockIdx.x / (p.splits * p.row_tiles);
-    const int M = p.m_rows, nq = p.nq;
-
-    // paged: one table and one length per sequence, shared by its heads
-    const int seq = PAGED ? slab / pp.heads_kv : slab, head = PAGED ? slab % pp.heads_kv : 0;
-
-    int len = p.nk;
-    if (p.kv_lens != nullptr) len = min(max(p.kv_lens[seq], 0), p.nk);
-
-    const int row0 = tile * kKvRowTile, rlast = min(row0 + kKvRowTile - 1, M - 1);
-    const int kbeg = s_idx * p.share;
-    int kend = min(kbeg + p.share, len);
-    if (CAUSAL) {   // bottom-right aligned: query i sees keys j <= len - nq + i; the tile's widest row bounds what the workgroup reads
-        const int imax = (row0 / nq != rlast / nq) ? nq - 1 : rlast % nq;
-        kend = min(kend, len - nq + imax + 1);
-    }
-    const int64_t rows_total = (int64_t)p.bh_kv * M;
-    const int64_t prow0 = (int64_t)slab * M + row0;        // first packed row of the tile, over all slabs
-    const int nblk = kend > kbeg ? (kend - kbeg + kKvBlk - 1) / kKvBlk : 0;
-
-    if (nblk == 0 && p.splits > 1) {   // the share lies beyond len or above the tile's diagonal: its O partial stays unwritten, the combine drops it
-        if (threadIdx.x < kKvRowTile && row0 + (int)threadIdx.x < M) p.lse_part[(int64_t)s_idx * rows_total + prow0 + threadIdx.x] = -INFINITY;
+    const KvTile tl = kv_tile<CAUSAL>(p, PAGED ? pp.heads_kv : 1);
+    if (kv_share_is_empty(p, tl)) {
+        kv_mark_share_empty(p, tl);
         return;
     }
-
-    const bool row_ok = row0 + lq < M;
-    int lim = kend - 1;   // last key this lane's row sees
-    if (CAUSAL) lim = min(lim, len - nq + (row0 + lq) % nq);
+    const bool row_ok = kv_row_ok(p, tl, lq);
+    const int lim = kv_last_visible_key<CAUSAL>(p, tl, lq);
+    const int slab = tl.slab, seq = tl.seq, head = tl.head, kbeg = tl.kbeg, kend = tl.kend, nblk = tl.nblk;
 
     bf16x8 qf[KS];
-    {
-        const __bf16* qr = (const __bf16*)p.q + (prow0 + (row_ok ? lq : 0)) * D + hi * 8;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            qf[ks] = *(const bf16x8*)(qr + ks * 16);
-            if (!row_ok)   // rows past M: computed on zeros, never stored
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[ks][e] = (__bf16)0.0f;
-        }
-    }
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = kv_q_fragment<D>(p.q, tl.prow0, row_ok, lq, hi, ks);
     bf16x8 ones;
 #pragma unroll
     for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
@@ -160,39 +119,16 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
 
-    // ---- paged: fa_paged_decode.hip's table handling ----
-    // The table entries of the block that starts at key kv0, issued back to back; only called with kend >= 1.  The empty statement pins the
-    // reads behind the statements before it.
-    auto fetch_pages = [&](int kv0, int(&e)[NP]) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            int idx = __builtin_amdgcn_readfirstlane(min(kv0 + i * kPagedMinPage, kend - 1)) >> pp.page_shift;
-            asm volatile("" : "+s"(idx));
-            e[i] = tbl[idx];
-        }
-    };
-    // ... and the point up to which they must have arrived: the end of the NEXT step.  The empty statements keep the compiler from using an
-    // entry (and so from waiting for it) any earlier.  Then the page offsets, in bytes.
-    auto pages_landed = [&](int(&e)[NP], int64_t(&pb)[NP]) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) asm volatile("" : "+s"(e[i]));
-#pragma unroll
-        for (int i = 0; i < NP; ++i) pb[i] = (int64_t)e[i] * pp.page_stride;
-    };
-
-    // The bytes of one block: K as KS 8-byte pieces for each of the lane's two keys, V as NV 16-byte pieces.
+    // The bytes of one block: K as KS 8-byte pieces for each of the lane's two keys, V as NV 16-byte pieces.  pb: its page offsets (PAGED)
     auto load_block = [&](int kv0, const int64_t(&pb)[NP], u32x2(&kf)[2][KS], u32x4(&vf)[NV]) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            const int row = min(kv0 + kb * 32 + lq, kend - 1);   // key kb * 32 + lq of the block: 16-key group 2 kb + (lq >> 4)
+            const int row = min(kv0 + kb * 32 + lq, kend - 1);
             const uint8_t* kr;
-            if constexpr (PAGED) {
-                // (a select between the two array elements themselves becomes an indexed read of the array: scratch)
-                const int64_t page = pb[2 * kb] + ((lq & 16) ? pb[2 * kb + 1] - pb[2 * kb] : (int64_t)0);
-                kr = kg + page + (unsigned)(row & page_mask) * row_stride + hi * 8;
-            } else {
+            if constexpr (PAGED)
+                kr = kg + page_of_k_row(pb, kb, lq) + (unsigned)(row & page_mask) * row_stride + hi * 8;
+            else
                 kr = kg + (int64_t)row * D + hi * 8;
-            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) kf[kb][ks] = *(const u32x2*)(kr + ks * 16);
         }
@@ -210,7 +146,7 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
 
     // One block.  The K and V bytes ping-pong between two register sets by NAME (the loop below is unrolled by two): a copy "current = next"
     // at the end of a step would have to wait for the next block's loads.
-    // Paged: the table runs two blocks ahead of the loads: pg[] holds the page offsets of the block whose loads the next step issues, ent[]
+    // PAGED: the table runs two blocks ahead of the loads: pg[] holds the page offsets of the block whose loads the next step issues, ent[]
     // the entries of the block after that, in flight from the end of one step to the end of the next.
     int64_t pg[NP];
     int ent[NP];
@@ -245,7 +181,9 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
             *(bf16x8*)(dst + v_wr_hi) = cvt_fp8x8(vcur[i][2], vcur[i][3]);
         }
 
-        // exp2 domain, mask (branch-free), row maximum
+        bf16x8 ph[4], pl[4];
+        // kv_mask_and_max (fa_kv_decode_core.h) written out: called as a function here, hipcc moves four of this file's sixteen kernels off
+        // their recorded instruction profile (two VGPRs more, other vmcnt waits), and tests/test_kv_code_profile.py holds them to it
         const int rel = lim - kv0 - 4 * hi;   // key offset (kb * 32 + (r & 3) + 8 * (r >> 2)) > rel: not visible
         float mx = -INFINITY;
 #pragma unroll
@@ -267,19 +205,7 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
             for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
 #pragma unroll
         for (int r = 0; r < 16; ++r) lacc[r] *= alpha;
-
-        bf16x8 ph[4], pl[4];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pe = fast_exp2(s[kb][8 * t + e] - m_use);
-                    const __bf16 h = (__bf16)pe;
-                    ph[kb * 2 + t][e] = h;
-                    pl[kb * 2 + t][e] = (__bf16)(pe - (float)h);
-                }
+        kv_p_terms(s, m_use, ph, pl);
 
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -305,8 +231,8 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
 #pragma unroll
             for (int db = 0; db < DB; ++db) asm volatile("" : "+v"(o[db]));
             asm volatile("" : "+v"(lacc));
-            pages_landed(ent, pg);                                // the block the next step issues: fetched a step ago
-            fetch_pages(kv0 + 3 * kKvWaves * kKvBlk, ent);        // the block after that
+            pages_landed(ent, pp.page_stride, pg);                                        // the block the next step issues: fetched a step ago
+            fetch_pages(tbl, pp.page_shift, kv0 + 3 * kKvWaves * kKvBlk, kend, ent);      // the block after that
         }
     };
 
@@ -314,16 +240,16 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
     u32x4 va[NV], vb[NV];
 #pragma unroll
     for (int i = 0; i < NP; ++i) pg[i] = 0, ent[i] = 0;
-    if (wave < nblk) {   // kend >= 1 from here on: every row (and, paged, every table index) is that of a key below len
+    if (wave < nblk) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
         if constexpr (PAGED) {
             int e0[NP], e1[NP];
-            fetch_pages(kbeg + wave * kKvBlk, e0);
-            fetch_pages(kbeg + (wave + kKvWaves) * kKvBlk, e1);
+            fetch_pages(tbl, pp.page_shift, kbeg + wave * kKvBlk, kend, e0);
+            fetch_pages(tbl, pp.page_shift, kbeg + (wave + kKvWaves) * kKvBlk, kend, e1);
             int64_t p0[NP];
-            pages_landed(e0, p0);
+            pages_landed(e0, pp.page_stride, p0);
             load_block(kbeg + wave * kKvBlk, p0, ka, va);
-            pages_landed(e1, pg);
-            fetch_pages(kbeg + (wave + 2 * kKvWaves) * kKvBlk, ent);
+            pages_landed(e1, pp.page_stride, pg);
+            fetch_pages(tbl, pp.page_shift, kbeg + (wave + 2 * kKvWaves) * kKvBlk, kend, ent);
         } else {
             load_block(kbeg + wave * kKvBlk, pg, ka, va);
         }
@@ -333,79 +259,8 @@ __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Param
         if (blk + kKvWaves < nblk) step(blk + kKvWaves, kb_, vb, ka, va);
     }
 
-    // ---- merge of the four waves: (m, l, O) of each through LDS (the wave's own V image: its last reads have been consumed) ----
-    mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight
-    {
-        float* ow = (float*)vbuf + lq * C::kMergeStride + 4 * hi;
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 pk;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pk[e] = o[db][4 * g + e];
-                *(f32x4*)(ow + db * 32 + 8 * g) = pk;
-            }
-        if (hi == 0) {
-            m_s[wave][lq] = m;
-            l_s[wave][lq] = lacc[0];
-        }
-    }
-    __syncthreads();
-
-    const int row = threadIdx.x >> 3, j = threadIdx.x & 7;   // 8 threads per row, D / 32 four-column pieces each
-    if (row0 + row >= M) return;
-    float mw[kKvWaves], a[kKvWaves];
-    float mt = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kKvWaves; ++w) {
-        mw[w] = m_s[w][row];
-        mt = fmaxf(mt, mw[w]);
-    }
-    float lt = 0.0f;
-#pragma unroll
-    for (int w = 0; w < kKvWaves; ++w) {
-        a[w] = (mw[w] == -INFINITY) ? 0.0f : fast_exp2(mw[w] - mt);
-        lt = __builtin_fmaf(a[w], l_s[w][row], lt);
-    }
-    const bool none = !(lt > 0.0f);   // no visible key in this share: O = 0, LSE = -inf
-    const int64_t prow = prow0 + row;
-    const int64_t orow = (p.splits > 1 ? (int64_t)s_idx * rows_total : 0) + prow;
-    const float v_scale = p8.v_scale;
-#pragma unroll
-    for (int i = 0; i < DB; ++i) {
-        const int col = (j + 8 * i) * 4;
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int w = 0; w < kKvWaves; ++w) {
-            const f32x4 x = *(const f32x4*)((const float*)(smem + w * C::kWaveLds) + row * C::kMergeStride + col);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(a[w], x[e], acc[e]);   // the same operation sequence as lt: acc == lt where V is constant 1
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = none ? 0.0f : acc[e] / lt;
-        if (p.splits > 1) {   // unscaled: fa_kv8_combine.hip multiplies by v_scale, behind ITS quotient
-            *(f32x4*)(p.o_part + orow * D + col) = acc;
-            continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] *= v_scale;   // behind the quotient: exactly v_scale where V is constant 1
-        if (OUT_F32) {
-            *(f32x4*)((float*)p.o + orow * D + col) = acc;
-        } else {
-            bf16x4 r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = (__bf16)acc[e];
-            *(bf16x4*)((__bf16*)p.o + orow * D + col) = r;
-        }
-    }
-    if (j == 0) {
-        const float lse = none ? -INFINITY : (mt + __builtin_amdgcn_logf(lt)) * kLn2;   // of the scaled scores: no v_scale
-        if (p.splits > 1)
-            p.lse_part[orow] = lse;
-        else if (p.lse != nullptr)
-            p.lse[prow] = lse;
-    }
+    mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight; the image's last reads have been consumed
+    kv_merge_and_store<D, OUT_F32, true, C::kWaveLds>(p, tl, smem, m_s, l_s, wave, lq, hi, m, o, lacc, p8.v_scale);
 }
 
 template <int D, bool PAGED>

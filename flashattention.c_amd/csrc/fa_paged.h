@@ -1,6 +1,7 @@
 // fa_paged.h -- what the translation units of libflashattn_amd_paged.so share (include/flashattn_amd_paged.h is the boundary).  The library is
 // the KV-cache forward of fa_kv.h over a paged cache: the plan (kv_plan), the launch parameters of the merge (KvParams) and the merge kernel
-// itself (fa_kv_combine.hip, compiled once and linked into both libraries) are that library's; the decode kernel is its own.
+// itself (fa_kv_combine.hip, compiled once and linked into both libraries) are that library's; the decode kernel is its own instance of the
+// 16-bit loop (fa_kv_decode16_body.h).
 #pragma once
 #include "fa_kv.h"
 

@@ -1,55 +1,10 @@
-// fa_paged_host.cpp -- the host side behind include/flashattn_amd_paged.h: argument validation (no device is touched before it passes; the
-// block table and the lengths are device memory and never dereferenced here) and the entry points.  The plan is fa_kv.h's kv_plan over
-// bh_kv = batch * heads_kv: splits, share and workspace are what libflashattn_amd_kv.so reports for the same shapes.
-#include "fa_paged.h"
-#include "flashattn_amd_paged.h"
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
+// fa_paged_host.cpp -- the entry points of include/flashattn_amd_paged.h over fa_kv_host.h (validation, plan, launch parameters).
+#include "fa_kv_host.h"
 
 namespace fa {
 
-static thread_local char g_paged_error[320] = "";
-
-static int paged_fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_paged_error, sizeof(g_paged_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// the shape part of the validation, shared by every entry point: fa_kv_plan.cpp's check_shape over bh_kv = batch * heads_kv
-static int check_shape(int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t dtype)
-{
-    if (batch < 1 || heads_kv < 1 || group < 1 || nq < 1 || nk < 1) return paged_fail(FA_ERR_INVALID_ARGUMENT, "batch, heads_kv, group, nq and nk must be >= 1");
-    if (dtype == FA_DTYPE_F32) return paged_fail(FA_ERR_UNSUPPORTED, "FA_DTYPE_F32 is not supported: caches are 16-bit (FA_DTYPE_BF16, FA_DTYPE_BF16_OUT_F32)");
-    if (dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_BF16_OUT_F32) return paged_fail(FA_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    if (d != 64 && d != 128) return paged_fail(FA_ERR_UNSUPPORTED, "head dim %d is not supported: 64 or 128", d);
-    if (nk > (1 << 24)) return paged_fail(FA_ERR_UNSUPPORTED, "nk = %lld exceeds 2^24", (long long)nk);
-    if (nq > (1 << 30) || (int64_t)group * nq > (1 << 30)) return paged_fail(FA_ERR_UNSUPPORTED, "group * nq exceeds 2^30");
-    if (batch > 0x7fffffffLL || batch * heads_kv > 0x7fffffffLL || batch * heads_kv * group > 0x7fffffffLL)
-        return paged_fail(FA_ERR_UNSUPPORTED, "batch * heads_kv * group exceeds 2^31 - 1");
-    const int64_t bh_kv = batch * heads_kv;
-    const KvPlan pl = kv_plan(bh_kv, group, nq, nk);
-    if (bh_kv * pl.row_tiles * pl.splits > 0x7fffffffLL) return paged_fail(FA_ERR_UNSUPPORTED, "the launch would exceed 2^31 - 1 workgroups");
-    return FA_OK;
-}
-
-static int check_page_size(int32_t page_size)
-{
-    if (page_size < kPagedMinPage || page_size > kPagedMaxPage || (page_size & (page_size - 1)) != 0)
-        return paged_fail(FA_ERR_UNSUPPORTED, "page_size %d is not supported: a power of two, %d .. %d rows", page_size, kPagedMinPage, kPagedMaxPage);
-    return FA_OK;
-}
-
-static bool overlaps(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
+static thread_local KvError g_paged_error;
+static const KvWords kPagedWords = {2, "batch, heads_kv", "caches are 16-bit", "batch * heads_kv * group", "fa_paged_workspace_bytes", "k", "v", "q, k, v, o"};
 
 }  // namespace fa
 
@@ -60,14 +15,14 @@ extern "C" {
 size_t fa_paged_workspace_bytes(int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t causal, int32_t dtype)
 {
     (void)causal;
-    if (check_shape(batch, heads_kv, group, nq, nk, d, dtype) != FA_OK) return 0;
+    if (check_shape(g_paged_error, kPagedWords, batch, heads_kv, group, nq, nk, d, dtype) != FA_OK) return 0;
     return kv_workspace_bytes(kv_plan(batch * heads_kv, group, nq, nk), batch * heads_kv, group, nq, d);
 }
 
 int32_t fa_paged_splits_for(int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t causal, int32_t dtype)
 {
     (void)causal;
-    if (check_shape(batch, heads_kv, group, nq, nk, d, dtype) != FA_OK) return 0;
+    if (check_shape(g_paged_error, kPagedWords, batch, heads_kv, group, nq, nk, d, dtype) != FA_OK) return 0;
     return kv_plan(batch * heads_kv, group, nq, nk).splits;
 }
 
@@ -75,93 +30,27 @@ const char* fa_paged_kernel_name_for(int64_t batch, int32_t heads_kv, int32_t gr
                                      int32_t page_size)
 {
     (void)causal;
-    if (check_shape(batch, heads_kv, group, nq, nk, d, dtype) != FA_OK || check_page_size(page_size) != FA_OK) return nullptr;
+    if (check_shape(g_paged_error, kPagedWords, batch, heads_kv, group, nq, nk, d, dtype) != FA_OK || check_page_size(g_paged_error, page_size) != FA_OK)
+        return nullptr;
     return paged_decode_kernel_name();   // one family: the page size is a launch parameter
 }
 
 int fa_paged_forward(const void* q, const fa_paged_cache* cache, void* o, float* lse, int64_t batch, int32_t heads_kv, int32_t group, int64_t nq,
                      int64_t nk, int32_t d, float scale, int32_t causal, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream)
 {
-    g_paged_error[0] = 0;
-    if (q == nullptr || cache == nullptr || o == nullptr) return paged_fail(FA_ERR_INVALID_ARGUMENT, "null pointer: q, cache and o are required");
-    const fa_paged_cache& c = *cache;
-    if (c.k_pool == nullptr || c.v_pool == nullptr || c.block_table == nullptr)
-        return paged_fail(FA_ERR_INVALID_ARGUMENT, "null pointer: k_pool, v_pool and block_table are required");
-    if (const int rc = check_shape(batch, heads_kv, group, nq, nk, d, dtype)) return rc;
-    if (const int rc = check_page_size(c.page_size)) return rc;
-    if (c.num_pages < 1 || c.num_pages > 0x7fffffffLL) return paged_fail(FA_ERR_INVALID_ARGUMENT, "num_pages = %lld outside 1 .. 2^31 - 1", (long long)c.num_pages);
-    if (c.max_pages < 1) return paged_fail(FA_ERR_INVALID_ARGUMENT, "max_pages must be >= 1");
-    if (nk > (int64_t)c.max_pages * c.page_size)
-        return paged_fail(FA_ERR_INVALID_ARGUMENT, "nk = %lld exceeds max_pages * page_size = %lld", (long long)nk, (long long)c.max_pages * c.page_size);
-    if ((c.page_stride | c.row_stride | c.head_stride) & 7)
-        return paged_fail(FA_ERR_INVALID_ARGUMENT, "page_stride, row_stride and head_stride must be multiples of 8 elements (16 bytes)");
-    if (c.row_stride < d) return paged_fail(FA_ERR_INVALID_ARGUMENT, "row_stride = %lld is below d = %d", (long long)c.row_stride, d);
-    if (c.page_stride < 1 || c.head_stride < 0) return paged_fail(FA_ERR_INVALID_ARGUMENT, "page_stride must be >= 1 and head_stride >= 0");
-    if (c.page_stride > (1ll << 40) || c.head_stride > (1ll << 40) || c.row_stride > (1ll << 40))
-        return paged_fail(FA_ERR_UNSUPPORTED, "a stride exceeds 2^40 elements");
-    // what a lane adds to a page base in 32 bits: the row inside the page and the head
-    const uint64_t in_page = ((uint64_t)c.page_size * (uint64_t)c.row_stride + (uint64_t)(heads_kv - 1) * (uint64_t)c.head_stride) * 2u;
-    if (in_page >= (1ull << 32))
-        return paged_fail(FA_ERR_UNSUPPORTED, "the offset inside a page (page_size * row_stride * 2 bytes plus the head offset = %llu) must stay below 2^32 bytes",
-                          (unsigned long long)in_page);
-    if (!(std::isfinite(scale)) || scale == 0.0f) return paged_fail(FA_ERR_INVALID_ARGUMENT, "scale must be finite and non-zero");
-    if (((uintptr_t)q | (uintptr_t)c.k_pool | (uintptr_t)c.v_pool | (uintptr_t)o) & 15)
-        return paged_fail(FA_ERR_INVALID_ARGUMENT, "q, k_pool, v_pool, o must be 16-byte aligned");
-    if ((uintptr_t)lse & 3) return paged_fail(FA_ERR_INVALID_ARGUMENT, "lse must be 4-byte aligned");
-    if (((uintptr_t)c.block_table | (uintptr_t)c.seq_lens) & 3) return paged_fail(FA_ERR_INVALID_ARGUMENT, "block_table and seq_lens must be 4-byte aligned");
-    if ((uintptr_t)workspace & 255) return paged_fail(FA_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-
-    const int out_f32 = dtype == FA_DTYPE_BF16_OUT_F32;
-    const int64_t bh_kv = batch * heads_kv;
-    const size_t rows = (size_t)bh_kv * group * nq;
-    const size_t q_bytes = rows * d * 2, o_bytes = rows * d * (out_f32 ? 4 : 2), lse_bytes = rows * 4;
-    // a pool over its whole strided extent: the last page's base, the last row of the last head in it, one row
-    const size_t pool_bytes = ((size_t)(c.num_pages - 1) * (size_t)c.page_stride + (size_t)(c.page_size - 1) * (size_t)c.row_stride +
-                               (size_t)(heads_kv - 1) * (size_t)c.head_stride + (size_t)d) * 2;
-    const size_t table_bytes = (size_t)batch * (size_t)c.max_pages * 4, lens_bytes = c.seq_lens != nullptr ? (size_t)batch * 4 : 0;
-    auto hits_input = [&](const void* p, size_t n) {
-        return overlaps(p, n, q, q_bytes) || overlaps(p, n, c.k_pool, pool_bytes) || overlaps(p, n, c.v_pool, pool_bytes) ||
-               overlaps(p, n, c.block_table, table_bytes) || (lens_bytes != 0 && overlaps(p, n, c.seq_lens, lens_bytes));
-    };
-    if (hits_input(o, o_bytes)) return paged_fail(FA_ERR_INVALID_ARGUMENT, "o overlaps q, a pool (measured over its whole strided extent), the block table or seq_lens");
-    if (lse != nullptr && (hits_input(lse, lse_bytes) || overlaps(lse, lse_bytes, o, o_bytes)))
-        return paged_fail(FA_ERR_INVALID_ARGUMENT, "lse overlaps q, a pool, the block table, seq_lens or o");
-
-    KvPlan pl = kv_plan(bh_kv, group, nq, nk);
-    const size_t need = kv_workspace_bytes(pl, bh_kv, group, nq, d);
-    if (workspace == nullptr || workspace_bytes == 0) {   // no scratch: the unsplit launch
-        pl.splits = 1;
-        pl.share = (int32_t)((nk + 63) / 64 * 64);
-    } else {
-        if (workspace_bytes < need)
-            return paged_fail(FA_ERR_INVALID_ARGUMENT, "workspace of %zu bytes is too small: fa_paged_workspace_bytes() = %zu", workspace_bytes, need);
-        const size_t ws = need ? need : 1;
-        if (hits_input(workspace, ws) || overlaps(workspace, ws, o, o_bytes) || (lse != nullptr && overlaps(workspace, ws, lse, lse_bytes)))
-            return paged_fail(FA_ERR_INVALID_ARGUMENT, "the workspace overlaps a tensor of the call (pools over their whole extent, the block table)");
-    }
-
+    KvError& e = g_paged_error;
+    e.text[0] = 0;
+    const KvCall a = {q, o, lse, batch, heads_kv, group, nq, nk, d, dtype, workspace, workspace_bytes};
+    if (const int rc = check_pool(e, kPagedWords, a, cache)) return rc;
+    if (const int rc = check_scale(e, scale)) return rc;
     PagedParams pp{};
-    KvParams& p = pp.kv;
-    p.q = q, p.k = c.k_pool, p.v = c.v_pool, p.o = o, p.lse = lse, p.kv_lens = c.seq_lens;
-    p.m_rows = (int32_t)((int64_t)group * nq);
-    p.nq = (int32_t)nq, p.nk = (int32_t)nk, p.bh_kv = (int32_t)bh_kv;
-    p.row_tiles = pl.row_tiles, p.splits = pl.splits, p.share = pl.share;
-    p.scale_log2e = scale * kLog2e;
-    if (pl.splits > 1) {
-        p.o_part = (float*)workspace;
-        p.lse_part = p.o_part + (size_t)pl.splits * rows * d;
-    }
-    pp.table = c.block_table;
-    pp.page_stride = c.page_stride, pp.head_stride = c.head_stride, pp.row_stride = (int32_t)c.row_stride;
-    pp.max_pages = c.max_pages, pp.heads_kv = heads_kv;
-    pp.page_shift = __builtin_ctz((unsigned)c.page_size);
-    hipError_t e = launch_paged_decode(pp, d, causal != 0, out_f32, (hipStream_t)stream);
-    if (e == hipSuccess && pl.splits > 1) e = launch_kv_combine(p, d, out_f32, (hipStream_t)stream);
-    if (e != hipSuccess) return paged_fail(e == hipErrorNoDevice ? FA_ERR_NO_DEVICE : FA_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
-    return FA_OK;
+    if (const int rc = plan_pool(e, kPagedWords, a, *cache, scale, pp)) return rc;
+    hipError_t err = launch_paged_decode(pp, d, causal != 0, a.out_f32(), (hipStream_t)stream);
+    if (err == hipSuccess && pp.kv.splits > 1) err = launch_kv_combine(pp.kv, d, a.out_f32(), (hipStream_t)stream);
+    return launch_result(e, err);
 }
 
-const char* fa_paged_last_error(void) { return g_paged_error; }
+const char* fa_paged_last_error(void) { return g_paged_error.text; }
 
 const char* fa_paged_version(void) { return "flashattn_amd_paged abi 1 gfx950 (paged K/V-cache attention: block tables over a shared page pool)"; }
 
