@@ -11,8 +11,8 @@ namespace fa {
 template <int D, bool CAUSAL, bool OUT_F32>
 __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv_decode_kernel(KvParams p)
 {
-    constexpr bool PAGED = false;
-    constexpr int P_TERMS = FA_KV_P_TERMS;
+    constexpr bool PAGED = false, WINDOW = false;
+    constexpr int P_TERMS = FA_KV_P_TERMS, window_left = 0;
     constexpr PagedParams pp{};   // never read
 #include "fa_kv_decode16_body.h"
 }

@@ -8,6 +8,7 @@
 // The including kernel provides, in namespace fa, with fa_kv_decode_core.h included:
 //   D, CAUSAL, OUT_F32      its template parameters
 //   PAGED, P_TERMS          constexpr bool / int
+//   WINDOW, window_left     constexpr bool; an int (named only behind `if constexpr (WINDOW)` and as kv_tile's ignored argument otherwise)
 //   p                       const KvParams&
 //   pp                      const PagedParams& where PAGED; any PagedParams otherwise (it is named only behind `if constexpr (PAGED)`)
 //
@@ -19,6 +20,8 @@
 //      and V image) is in flight while block j is computed -- 4 waves x 32 KiB at d = 128, and the buffers are private to a wave, so
 //      the loop has no barrier.
 // PAGED differs in how a row's address is formed, and in nothing else: the results are the same bits on the gathered cache.
+// WINDOW (fa_kvw_decode.hip) differs in where the tile's shares start (kv_tile), in one more select per score (kv_mask_and_max) and in a
+// lower clamp max(., lo) beside the upper one on every K row, V row and table index: no load, product, exponential or LDS byte more.
     constexpr int NP = kPagedBlockPages;
     using C = KvCfg<D>;
     constexpr int KS = C::KS, DB = C::DB;
@@ -31,7 +34,7 @@
 
     int heads_kv = 1;
     if constexpr (PAGED) heads_kv = pp.heads_kv;
-    const KvTile tl = kv_tile<CAUSAL>(p, heads_kv);
+    const KvTile tl = kv_tile<CAUSAL, WINDOW>(p, heads_kv, window_left);
     if (kv_share_is_empty(p, tl)) {
         kv_mark_share_empty(p, tl);
         return;
@@ -39,6 +42,11 @@
     const bool row_ok = kv_row_ok(p, tl, lq);
     const int lim = kv_last_visible_key<CAUSAL>(p, tl, lq);
     const int slab = tl.slab, seq = tl.seq, head = tl.head, kbeg = tl.kbeg, kend = tl.kend, nblk = tl.nblk;
+    // WINDOW: the first key this lane's row sees, and the tile's (the lower clamp of every row that is loaded or looked up: kend > lo
+    // wherever nblk > 0, since the tile's widest row reaches beyond its lowest key)
+    int lo_row = 0;
+    if constexpr (WINDOW) lo_row = tl.diag + (tl.row0 + lq) % p.nq - window_left;
+    const int lo = tl.lo;
 
     bf16x8 qf[KS];
 #pragma unroll
@@ -81,7 +89,8 @@
     auto load_k = [&](int kv0, const int64_t(&pb)[NP], bf16x8(&kf)[2][KS]) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            const int row = min(kv0 + kb * 32 + lq, kend - 1);
+            int row = min(kv0 + kb * 32 + lq, kend - 1);
+            if constexpr (WINDOW) row = max(row, lo);
             const __bf16* kr;
             if constexpr (PAGED)
                 kr = kg + page_of_k_row(pb, kb, lq) + (unsigned)(row & page_mask) * row_stride + hi * 8;
@@ -101,10 +110,13 @@
                 const int col = cb * 16 + (lane & 1) * 8;
                 constexpr int kKeysPerPiece = 512 / D;   // a 1 KiB piece holds whole rows of 2 D bytes
                 static_assert(kPagedMinPage % kKeysPerPiece == 0, "a piece must not straddle a 16-key group");
-                const int row = min(kv0 + key, kend - 1);
+                int row = min(kv0 + key, kend - 1);
+                if constexpr (WINDOW) row = max(row, lo);
                 const __bf16* src = vg + pb[ch * kKeysPerPiece / kPagedMinPage] + (unsigned)(row & page_mask) * row_stride + col;
                 __builtin_amdgcn_global_load_lds((gbl_cvoid_t*)src, (lds_void_t*)(dst + ch * 1024), 16, 0, 0);
             }
+        } else if constexpr (WINDOW) {
+            issue_v_tile_from<D>(vg, kv0, lo, kend, dst, lane);
         } else {
             issue_v_tile<D, 1>(vg, kv0, kend, D, dst, 0, lane);
         }
@@ -135,7 +147,7 @@
             for (int kb = 0; kb < 2; ++kb) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kcur[kb][ks], qf[ks], s[kb], 0, 0, 0);
 
         bf16x8 ph[4], pl[4];
-        const KvRescale rs = kv_mask_and_max(s, lim - kv0 - 4 * hi, c, m);
+        const KvRescale rs = kv_mask_and_max<WINDOW>(s, lim - kv0 - 4 * hi, c, m, lo_row - kv0 - 4 * hi);
 #pragma unroll
         for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -170,7 +182,7 @@
             }
         if constexpr (PAGED) {
             pages_landed(ent, pp.page_stride, pg);                                        // the block the next step issues: fetched a step ago
-            fetch_pages(tbl, pp.page_shift, kv0 + 3 * kKvWaves * kKvBlk, kend, ent);      // the block after that
+            fetch_pages<WINDOW>(tbl, pp.page_shift, kv0 + 3 * kKvWaves * kKvBlk, kend, ent, lo);   // the block after that
         }
         asm volatile("" ::: "memory");   // the image is read before the next step's DMA may be enqueued over its twin
     };
@@ -180,14 +192,14 @@
     if (wave < nblk) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
         if constexpr (PAGED) {
             int e0[NP], e1[NP];
-            fetch_pages(tbl, pp.page_shift, kbeg + wave * kKvBlk, kend, e0);
-            fetch_pages(tbl, pp.page_shift, kbeg + (wave + kKvWaves) * kKvBlk, kend, e1);
+            fetch_pages<WINDOW>(tbl, pp.page_shift, kbeg + wave * kKvBlk, kend, e0, lo);
+            fetch_pages<WINDOW>(tbl, pp.page_shift, kbeg + (wave + kKvWaves) * kKvBlk, kend, e1, lo);
             int64_t p0[NP];
             pages_landed(e0, pp.page_stride, p0);
             load_k(kbeg + wave * kKvBlk, p0, kc);
             issue_v(kbeg + wave * kKvBlk, p0, vbuf);
             pages_landed(e1, pp.page_stride, pg);
-            fetch_pages(tbl, pp.page_shift, kbeg + (wave + 2 * kKvWaves) * kKvBlk, kend, ent);
+            fetch_pages<WINDOW>(tbl, pp.page_shift, kbeg + (wave + 2 * kKvWaves) * kKvBlk, kend, ent, lo);
         } else {
             load_k(kbeg + wave * kKvBlk, pg, kc);
             issue_v(kbeg + wave * kKvBlk, pg, vbuf);
@@ -201,4 +213,11 @@
 
     mfma_drain();     // the loop exit is a branch: the last matrix instructions may still be in flight
     wait_lds_dma();   // the last step's look-ahead still targets an image; after it the merge may take the wave's V images
+    // hipcc cannot see that wait (it is inline asm) and adds one of its own where the merge first overwrites a register the look-ahead K loads
+    // target -- at the top of the merge, or inside its `hi == 0` branch and again behind it, as the register allocation falls.  The d = 128
+    // kernels of the unwindowed libraries have the one at the top; a wait hipcc can see puts the windowed ones' there whatever the allocation is.
+    if constexpr (WINDOW && D == 128) {
+        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0) alone
+        __builtin_amdgcn_sched_barrier(0);    // ... and nothing of the merge is scheduled in front of it
+    }
     kv_merge_and_store<D, OUT_F32, false, C::kWaveLds>(p, tl, smem, m_s, l_s, wave, lq, hi, m, o, lacc, 1.0f);

@@ -1,7 +1,9 @@
-// fa_kv_decode_core.h -- the device pieces the decode kernels of the three KV-cache libraries are made of: few query rows against many cached
+// fa_kv_decode_core.h -- the device pieces the decode kernels of the KV-cache libraries are made of: few query rows against many cached
 // keys (decode, chunked prefill, cross-attention, GQA), the bandwidth-bound twin of the square kernels.  No counterpart in the reference, whose
-// one entry computes square self-attention.  Users: fa_kv_decode16_body.h (the 16-bit loop of fa_kv_decode.hip and fa_paged_decode.hip) and
-// fa_kv8_decode.hip.  Every piece is forced inline; nothing here branches at run time on the kind of cache.
+// one entry computes square self-attention.  Users: fa_kv_decode16_body.h (the 16-bit loop of fa_kv_decode.hip, fa_paged_decode.hip and, with
+// WINDOW = true, fa_kvw_decode.hip) and fa_kv8_decode.hip.  Every piece is forced inline; nothing here branches at run time on the kind of
+// cache, and what a sliding window adds sits behind `if constexpr (WINDOW)`: with WINDOW = false (the default of every piece) the text is
+// what it was.
 //
 // The pieces return values and take values (not references to the kernel's arguments or accumulators) wherever they can, and the kernels keep
 // what hipcc compiles to other code once it is a function of its own -- the empty share's `return`, the rescale of the accumulators, the P.V
@@ -48,13 +50,17 @@ struct KvTile {
     int diag;                // len - nq.  Causal is bottom-right aligned: query i sees keys j <= diag + i
     int row0;                // first packed row of the tile within its slab
     int kbeg, kend, nblk;    // the keys [kbeg, kend) this workgroup reads, in nblk 64-key blocks
+    int lo;                  // WINDOW: the tile's lowest visible key (kbeg <= lo only in the tile's first share); 0 otherwise
     int64_t rows_total;      // packed rows over all slabs
     int64_t prow0;           // first packed row of the tile, over all slabs
 };
 
 // heads_kv: the slabs that share one length (and, paged, one table): 1 for a contiguous cache, the K/V heads of a sequence for a paged one.
-template <bool CAUSAL>
-__device__ __forceinline__ KvTile kv_tile(const KvParams& p, int heads_kv)
+// WINDOW (the sliding-window kernels of fa_kvw_decode.hip; include/flashattn_amd_kvw.h): query i sees no key below diag + i - window_left.
+// The tile's lowest visible key is lo = max(0, diag + imin - window_left), imin the smallest query index among the tile's rows, and the
+// shares are laid over the keys from lo & ~63 on instead of from 0 -- blocks still start at multiples of 64 keys.
+template <bool CAUSAL, bool WINDOW = false>
+__device__ __forceinline__ KvTile kv_tile(const KvParams& p, int heads_kv, int window_left = 0)
 {
     const int s_idx = blockIdx.x % p.splits;
     const int tile = (blockIdx.x / p.splits) % p.row_tiles;
@@ -67,9 +73,14 @@ __device__ __forceinline__ KvTile kv_tile(const KvParams& p, int heads_kv)
     if (p.kv_lens != nullptr) len = min(max(p.kv_lens[seq], 0), p.nk);
 
     const int row0 = tile * kKvRowTile, rlast = min(row0 + kKvRowTile - 1, M - 1);
-    const int kbeg = s_idx * p.share;
-    int kend = min(kbeg + p.share, len);
     const int diag = len - nq;
+    int kbeg = s_idx * p.share, lo = 0;
+    if constexpr (WINDOW) {
+        const int imin = (row0 / nq != rlast / nq) ? 0 : row0 % nq;
+        lo = max(diag + imin - window_left, 0);
+        kbeg += lo & ~(kKvBlk - 1);
+    }
+    int kend = min(kbeg + p.share, len);
     if (CAUSAL) {   // the tile's widest row bounds what the workgroup reads
         const int imax = (row0 / nq != rlast / nq) ? nq - 1 : rlast % nq;
         kend = min(kend, diag + imax + 1);
@@ -77,7 +88,7 @@ __device__ __forceinline__ KvTile kv_tile(const KvParams& p, int heads_kv)
     const int64_t rows_total = (int64_t)p.bh_kv * M;
     const int64_t prow0 = (int64_t)slab * M + row0;
     const int nblk = kend > kbeg ? (kend - kbeg + kKvBlk - 1) / kKvBlk : 0;
-    return KvTile{s_idx, tile, slab, seq, head, len, diag, row0, kbeg, kend, nblk, rows_total, prow0};
+    return KvTile{s_idx, tile, slab, seq, head, len, diag, row0, kbeg, kend, nblk, lo, rows_total, prow0};
 }
 
 // The share lies beyond len or above the tile's diagonal: the kernel says so in the share's LSE partial and returns -- its O partial stays
@@ -110,18 +121,21 @@ __device__ __forceinline__ bf16x8 kv_q_fragment(const void* q, int64_t prow0, bo
 // ---- one block's softmax step, in two pieces with the rescale of the accumulators between them in the kernel ----
 // first: exp2 domain, mask (branch-free: the vector ALU idles in these kernels), row maximum; s becomes the masked scores, m the new maximum.
 // rel = lim - kv0 - 4 * hi: key offset (kb * 32 + (r & 3) + 8 * (r >> 2)) > rel is not visible
+// WINDOW: rel_lo = (diag + i - window_left) - kv0 - 4 * hi: neither is a key offset < rel_lo -- one more select on the score, no branch
 struct KvRescale {
     float m_use;   // what the exponentials of this block refer to
     float alpha;   // what the accumulators are multiplied by
 };
-__device__ __forceinline__ KvRescale kv_mask_and_max(f32x16 (&s)[2], int rel, float c, float& m)
+template <bool WINDOW = false>
+__device__ __forceinline__ KvRescale kv_mask_and_max(f32x16 (&s)[2], int rel, float c, float& m, int rel_lo = 0)
 {
     float mx = -INFINITY;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float t = (kb * 32 + (r & 3) + 8 * (r >> 2) > rel) ? -INFINITY : s[kb][r] * c;
+            float t = (kb * 32 + (r & 3) + 8 * (r >> 2) > rel) ? -INFINITY : s[kb][r] * c;
+            if constexpr (WINDOW) t = (kb * 32 + (r & 3) + 8 * (r >> 2) < rel_lo) ? -INFINITY : t;
             s[kb][r] = t;
         }
 #pragma unroll
@@ -242,11 +256,15 @@ __device__ __forceinline__ void kv_merge_and_store(const KvParams& p, const KvTi
 // The table entries of the block that starts at key kv0, issued back to back; only called with kend >= 1.  The empty statement pins the
 // reads behind the statements before it: lgkmcnt counts them together with the LDS reads, so a read issued before the step's last
 // "s_waitcnt lgkmcnt(0)" would have the matrix pipe wait for a table round trip.
-__device__ __forceinline__ void fetch_pages(cst_i32_t* tbl, int page_shift, int kv0, int kend, int (&e)[kPagedBlockPages])
+// WINDOW: the row is clamped from below to the tile's lowest visible key as well, so no entry below lo >> page_shift is read either.
+template <bool WINDOW = false>
+__device__ __forceinline__ void fetch_pages(cst_i32_t* tbl, int page_shift, int kv0, int kend, int (&e)[kPagedBlockPages], int lo = 0)
 {
 #pragma unroll
     for (int i = 0; i < kPagedBlockPages; ++i) {
-        int idx = __builtin_amdgcn_readfirstlane(min(kv0 + i * kPagedMinPage, kend - 1)) >> page_shift;
+        int row = min(kv0 + i * kPagedMinPage, kend - 1);
+        if constexpr (WINDOW) row = max(row, lo);
+        int idx = __builtin_amdgcn_readfirstlane(row) >> page_shift;
         asm volatile("" : "+s"(idx));
         e[i] = tbl[idx];
     }
@@ -276,6 +294,23 @@ struct KvCfg {
     static constexpr int kLoadsPerBlock = 2 * KS + kVTile / 1024;   // vector-memory instructions per lane and block: K fragments + V pieces
     static_assert(kLoadsPerBlock <= 63, "vmcnt holds 6 bits");   // what the loop waits for: "only the next block's loads are outstanding"
 };
+
+// issue_v_tile<D, 1> (fa_bf16_common.h, which the product kernels compile and which stays as it is) with the window's lower clamp: rows
+// below lo load row lo, rows at or beyond n load row n - 1.  The same pieces, the same order, the same addresses for rows inside [lo, n).
+template <int D>
+__device__ __forceinline__ void issue_v_tile_from(const __bf16* __restrict__ vg, int kv0, int lo, int n, char* dst, int lane)
+{
+#pragma unroll
+    for (int ch = 0; ch < kKvBlk * 2 * D / 1024; ++ch) {
+        const int blk = ch * 8 + lane / 8;
+        const int kg4 = blk / (D / 16), cb = blk % (D / 16);
+        const int key = kg4 * 4 + (lane % 8) / 2;
+        const int col = cb * 16 + (lane & 1) * 8;
+        const int grow = max(min(kv0 + key, n - 1), lo);
+        const __bf16* src = vg + (int64_t)grow * D + col;
+        __builtin_amdgcn_global_load_lds((gbl_cvoid_t*)src, (lds_void_t*)(dst + ch * 1024), 16, 0, 0);
+    }
+}
 
 template <int N>
 __device__ __forceinline__ void wait_vm_outstanding() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

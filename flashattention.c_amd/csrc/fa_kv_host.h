@@ -1,7 +1,7 @@
-// fa_kv_host.h -- the host side the three KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp): argument validation
+// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp): argument validation
 // (no device is touched before it passes; lengths and block tables are device memory and never dereferenced here), the workspace and the
 // plan it selects, and the fill of the launch parameters.  Inline, like kv_plan: the libraries link no host object of each other.  The plan
-// is fa_kv.h's kv_plan over bh_kv = batch * heads_kv, so splits, share and workspace are the same in all three for the same shapes.
+// is fa_kv.h's kv_plan over bh_kv = batch * heads_kv, so splits, share and workspace are the same in all of them for the same shapes (the windowed library: for the same span).
 // Each library keeps its entry points, its version string and its own thread-local error text (KvError), and passes in the few words in
 // which its messages differ (KvWords).  tests/test_kv_host_errors.py holds every check to its code and its text.
 #pragma once
@@ -149,15 +149,17 @@ inline int check_alignment(KvError& e, const KvCall& a, const void* k, const voi
 }
 
 // The plan of the call -- unsplit where it comes without a workspace -- and how much of the workspace the kernels use (*ws: 0 without one,
-// at least 1 with one, so that a workspace the plan does not need is still kept off the tensors).
-inline int plan_call(KvError& e, const KvWords& w, const KvCall& a, KvPlan& pl, size_t* ws)
+// at least 1 with one, so that a workspace the plan does not need is still kept off the tensors).  span: the keys the plan is laid over --
+// nk (0), or the widest key range of a row tile where a window bounds it from below (fa_kvw.h).
+inline int plan_call(KvError& e, const KvWords& w, const KvCall& a, KvPlan& pl, size_t* ws, int64_t span = 0)
 {
-    pl = kv_plan(a.bh_kv(), a.group, a.nq, a.nk);
+    if (span == 0) span = a.nk;
+    pl = kv_plan(a.bh_kv(), a.group, a.nq, span);
     const size_t need = kv_workspace_bytes(pl, a.bh_kv(), a.group, a.nq, a.d);
     *ws = 0;
     if (a.workspace == nullptr || a.workspace_bytes == 0) {   // no scratch: the unsplit launch
         pl.splits = 1;
-        pl.share = (int32_t)((a.nk + 63) / 64 * 64);
+        pl.share = (int32_t)((span + 63) / 64 * 64);
         return FA_OK;
     }
     if (a.workspace_bytes < need)
@@ -182,7 +184,7 @@ inline void fill_params(const KvCall& a, const KvPlan& pl, float scale, KvParams
 
 // 2 (contiguous cache): alignment, overlap, workspace; then the launch parameters
 inline int plan_cache(KvError& e, const KvWords& w, const KvCall& a, const void* k, const void* v, int64_t capacity, const int32_t* kv_lens, float scale,
-                      KvParams& p)
+                      KvParams& p, int64_t span = 0)
 {
     if (const int rc = check_alignment(e, a, k, v, (uintptr_t)kv_lens, w.qkvo, "kv_lens")) return rc;
     const size_t q_bytes = a.q_bytes(), o_bytes = a.o_bytes(), lse_bytes = a.lse_bytes(), kv_bytes = (size_t)a.bh_kv() * capacity * a.d * w.elem;
@@ -193,7 +195,7 @@ inline int plan_cache(KvError& e, const KvWords& w, const KvCall& a, const void*
         return e.fail(FA_ERR_INVALID_ARGUMENT, "lse overlaps q, %s, %s or o", w.k, w.v);
     KvPlan pl;
     size_t ws;
-    if (const int rc = plan_call(e, w, a, pl, &ws)) return rc;
+    if (const int rc = plan_call(e, w, a, pl, &ws, span)) return rc;
     if (ws != 0 && (hits_input(a.workspace, ws) || overlaps(a.workspace, ws, a.o, o_bytes) || (a.lse != nullptr && overlaps(a.workspace, ws, a.lse, lse_bytes)) ||
                     (kv_lens != nullptr && overlaps(a.workspace, ws, kv_lens, (size_t)a.bh_kv() * 4))))
         return e.fail(FA_ERR_INVALID_ARGUMENT, "the workspace overlaps a tensor of the call");
@@ -204,7 +206,7 @@ inline int plan_cache(KvError& e, const KvWords& w, const KvCall& a, const void*
 }
 
 // 2 (paged cache)
-inline int plan_pool(KvError& e, const KvWords& w, const KvCall& a, const fa_paged_cache& c, float scale, PagedParams& pp)
+inline int plan_pool(KvError& e, const KvWords& w, const KvCall& a, const fa_paged_cache& c, float scale, PagedParams& pp, int64_t span = 0)
 {
     if (const int rc = check_alignment(e, a, c.k_pool, c.v_pool, (uintptr_t)c.block_table | (uintptr_t)c.seq_lens, "q, k_pool, v_pool, o", "block_table and seq_lens"))
         return rc;
@@ -223,7 +225,7 @@ inline int plan_pool(KvError& e, const KvWords& w, const KvCall& a, const fa_pag
         return e.fail(FA_ERR_INVALID_ARGUMENT, "lse overlaps q, a pool, the block table, seq_lens or o");
     KvPlan pl;
     size_t ws;
-    if (const int rc = plan_call(e, w, a, pl, &ws)) return rc;
+    if (const int rc = plan_call(e, w, a, pl, &ws, span)) return rc;
     if (ws != 0 && (hits_input(a.workspace, ws) || overlaps(a.workspace, ws, a.o, o_bytes) || (a.lse != nullptr && overlaps(a.workspace, ws, a.lse, lse_bytes))))
         return e.fail(FA_ERR_INVALID_ARGUMENT, "the workspace overlaps a tensor of the call (pools over their whole extent, the block table)");
     fill_params(a, pl, scale, pp.kv);

@@ -7,8 +7,8 @@ namespace fa {
 template <int D, bool CAUSAL, bool OUT_F32>
 __global__ __launch_bounds__(kKvWaves* kWave) void fa_paged_decode_kernel(PagedParams pp)
 {
-    constexpr bool PAGED = true;
-    constexpr int P_TERMS = 2;
+    constexpr bool PAGED = true, WINDOW = false;
+    constexpr int P_TERMS = 2, window_left = 0;
     const KvParams& p = pp.kv;
 #include "fa_kv_decode16_body.h"
 }

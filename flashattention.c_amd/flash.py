@@ -23,7 +23,7 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kvw, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -141,7 +141,7 @@ KV_HEAD_DIMS = (64, 128)
 
 def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
                kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None,
-               out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+               out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None, window_left: Optional[int] = None):
     """Attention of few query rows against a K/V cache (``include/flashattn_amd_kv.h``): decode, chunked prefill, cross-attention, GQA.
 
     ``q`` is ``(BHq, nq, d)``; ``k``, ``v`` are ``(BHkv, capacity, d)`` caches of which the first ``kv_len`` rows (default: all ``capacity``)
@@ -151,6 +151,13 @@ def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     visible key get ``O = 0``, ``LSE = -inf``.  bfloat16 tensors, ``d`` 64 or 128; ``out_dtype=torch.float32`` stores the fp32 accumulator.
     Arithmetic and accuracy are those of ``forward(..., out_dtype=torch.float32)`` on bf16 tensors (P as two bf16 terms) for both outputs.
     Scratch (``workspace_bytes_kv``; key-split launches only) comes from ``torch.empty`` unless ``workspace`` passes a ``torch.uint8`` tensor.
+
+    ``window_left`` (``include/flashattn_amd_kvw.h``; ``None``: no window) is a sliding window, read as flash-attn's ``window_size=(left, -1 | 0)``:
+    with ``len`` a slab's length, query row ``i`` sees key ``j`` iff ``j < len``, ``j >= len - nq + i - window_left`` and, when ``causal``,
+    ``j <= len - nq + i`` -- causal with ``window_left = W - 1`` is "the last ``W`` keys including my own".  An ``int >= 0``; negative raises
+    ``ValueError``.  The call walks only the keys of the window, so its time follows ``window_left``, not ``len``, and with
+    ``lo = max(0, len - nq - window_left)`` no K/V row below ``lo`` and none at or beyond ``len`` is ever read: rows that have slid out of
+    the window may hold anything.  Pass the same ``window_left`` to ``workspace_bytes_kv``.
     """
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
@@ -195,32 +202,53 @@ def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
         raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
     lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
-    L = _cabi_kv.lib()
+    window_left = _window(window_left)
+    L = _cabi_kv.lib() if window_left is None else _cabi_kvw.lib()
     with torch.cuda.device(q.device):
-        need = int(L.fa_kv_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        if window_left is None:
+            need = int(L.fa_kv_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        else:
+            need = int(L.fa_kvw_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt, window_left))
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
         elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
             raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
         stream = torch.cuda.current_stream().cuda_stream
-        rc = L.fa_kv_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                             bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
-                             d, float(scale), int(bool(causal)), dt,
-                             workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                             workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-    _cabi_kv.check(rc)
+        head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None, d, float(scale), int(bool(causal)), dt)
+        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+        rc = L.fa_kv_forward(*head, *tail) if window_left is None else L.fa_kvw_forward(*head, window_left, *tail)
+    (_cabi_kv if window_left is None else _cabi_kvw).check(rc)
     return (out, lse) if return_lse else out
 
 
-def workspace_bytes_kv(bh_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *, out_dtype: torch.dtype = torch.bfloat16) -> int:
-    """Bytes of scratch ``forward_kv`` can use for these shapes (``fa_kv_workspace_bytes``); 0 when the plan does not split the keys."""
+def _window(window_left: Optional[int]) -> Optional[int]:
+    """``window_left`` as the windowed entries take it: None (no window: the unwindowed libraries), or an int in 0 .. 2^24 (wider hides nothing)"""
+    if window_left is None:
+        return None
+    if isinstance(window_left, bool) or not isinstance(window_left, int):
+        raise TypeError(f"window_left must be None or an int, got {type(window_left).__name__}")
+    if window_left < 0:
+        raise ValueError(f"window_left = {window_left} must be >= 0 (None: no window)")
+    return min(window_left, 1 << 24)
+
+
+def workspace_bytes_kv(bh_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *, out_dtype: torch.dtype = torch.bfloat16,
+                       window_left: Optional[int] = None) -> int:
+    """Bytes of scratch ``forward_kv`` can use for these shapes (``fa_kv_workspace_bytes``) and this ``window_left`` (``fa_kvw_workspace_bytes``:
+    the plan is laid over ``min(nk, window_left + nq + 63)`` keys); 0 when the plan does not split the keys."""
     dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    window_left = _window(window_left)
+    if window_left is not None:
+        return int(_cabi_kvw.lib().fa_kvw_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt, window_left))
     return int(_cabi_kv.lib().fa_kv_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
 
 
 def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
                   seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None, scale: float = 1.0, return_lse: bool = False,
-                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None,
+                  window_left: Optional[int] = None):
     """``forward_kv`` over a paged cache (``include/flashattn_amd_paged.h``): K/V rows live in pages of a shared pool, found through a block table.
 
     ``k_pool``, ``v_pool`` are ``(pages, page, d)`` (one K/V head) or ``(pages, page, H, d)``; their strides are taken as they are, so a
@@ -231,6 +259,11 @@ def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, b
     device, gives each its own length (clamped to ``[0, kv_len]``).  Table and lengths are read by the kernel only, so one captured graph
     follows a cache that grows and whose pages move.  Pages of 16 .. 65536 rows, a power of two.  Everything else -- ``causal``, rows without
     keys, dtypes, arithmetic, scratch (``workspace_bytes_paged``) -- is ``forward_kv``'s, and so is the result, bit for bit, on the gathered cache.
+
+    ``window_left`` (``None``: no window) is ``forward_kv``'s sliding window: row ``i`` sees key ``j`` iff ``j < len``, ``j >= len - nq + i - window_left``
+    and, when ``causal``, ``j <= len - nq + i``.  With ``lo = max(0, len - nq - window_left)`` no pool row of a key below ``lo`` or at or beyond
+    ``len`` is read, and no table entry below ``lo // page`` or at or beyond ``ceil(len / page)``: pages that have slid out of the window can be
+    freed or reused, and their entries may hold anything.  Pass the same ``window_left`` to ``workspace_bytes_paged``.
     """
     for name, t in (("q", q), ("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
         if not isinstance(t, torch.Tensor):
@@ -290,26 +323,36 @@ def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, b
     lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
     cache = _cabi_paged.FaPagedCache(k_pool.data_ptr(), v_pool.data_ptr(), pages, page, page_stride, row_stride, head_stride,
                                      block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
-    L = _cabi_paged.lib()
+    window_left = _window(window_left)
+    L = _cabi_paged.lib() if window_left is None else _cabi_kvw.lib()
     with torch.cuda.device(q.device):
-        need = int(L.fa_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        if window_left is None:
+            need = int(L.fa_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        else:
+            need = int(L.fa_kvw_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt, window_left))
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
         elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
             raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
         stream = torch.cuda.current_stream().cuda_stream
-        rc = L.fa_paged_forward(q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                                batch, heads_kv, group, nq, nk, d, float(scale), int(bool(causal)), dt,
-                                workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-    _cabi_paged.check(rc)
+        head = (q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                batch, heads_kv, group, nq, nk, d, float(scale), int(bool(causal)), dt)
+        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+        rc = L.fa_paged_forward(*head, *tail) if window_left is None else L.fa_kvw_paged_forward(*head, window_left, *tail)
+    (_cabi_paged if window_left is None else _cabi_kvw).check(rc)
     return (out, lse) if return_lse else out
 
 
 def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *,
-                          out_dtype: torch.dtype = torch.bfloat16) -> int:
-    """Bytes of scratch ``forward_paged`` can use for these shapes (``fa_paged_workspace_bytes`` = ``workspace_bytes_kv`` at ``batch * heads_kv``)."""
+                          out_dtype: torch.dtype = torch.bfloat16, window_left: Optional[int] = None) -> int:
+    """Bytes of scratch ``forward_paged`` can use for these shapes (``fa_paged_workspace_bytes`` = ``workspace_bytes_kv`` at ``batch * heads_kv``)
+    and this ``window_left`` (``fa_kvw_paged_workspace_bytes``)."""
     dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
+    window_left = _window(window_left)
+    if window_left is not None:
+        return int(_cabi_kvw.lib().fa_kvw_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt,
+                                                                window_left))
     return int(_cabi_paged.lib().fa_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
 
 
