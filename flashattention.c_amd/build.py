@@ -12,6 +12,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
 ``libflashattn_amd_paged.so`` (paged KV-cache attention, include/flashattn_amd_paged.h; ``PAGED_SOURCES``) likewise.
 ``libflashattn_amd_kv8.so`` (both over an fp8 e4m3 cache, include/flashattn_amd_kv8.h; ``KV8_SOURCES``) likewise.
 ``libflashattn_amd_kvw.so`` (both 16-bit caches under a sliding window, include/flashattn_amd_kvw.h; ``KVW_SOURCES``) likewise.
+``libflashattn_amd_kvw8.so`` (the fp8 caches under a sliding window, include/flashattn_amd_kvw8.h; ``KVW8_SOURCES``) likewise.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
 They are NOT part of the product library: its ``fa_forward_ex`` rejects their variant numbers.
@@ -75,13 +76,18 @@ KV8_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv8.so")
 # instances of the 16-bit decode loop (WINDOW = true), its host side, and the OBJECT of the KV library's merge kernel, like the paged library.
 KVW_SOURCES = ["fa_kvw_decode.hip", "fa_kv_combine.hip", "fa_kvw_host.cpp"]
 KVW_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kvw.so")
+# libflashattn_amd_kvw8.so, sliding-window attention over the contiguous and the paged fp8 cache behind include/flashattn_amd_kvw8.h: its own
+# instances of the fp8 decode loop (WINDOW = true), its host side, and the OBJECT of the fp8 library's merge kernel (fa_kv8_combine.hip is compiled once).
+KVW8_SOURCES = ["fa_kvw8_decode.hip", "fa_kv8_combine.hip", "fa_kvw8_host.cpp"]
+KVW8_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kvw8.so")
 ABL_DRIVER_PATH = os.path.join(PKG_DIR, "fa_driver_ablation")
 # every header under csrc/ (globbed: a new header cannot be forgotten -- ADVICE r04) plus the C ABI
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [os.path.join(ROOT, "include", "flashattn_amd.h"),
                                                                                                                             os.path.join(ROOT, "include", "flashattn_amd_kv.h"),
                                                                                                                             os.path.join(ROOT, "include", "flashattn_amd_paged.h"),
                                                                                                                             os.path.join(ROOT, "include", "flashattn_amd_kv8.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kvw.h")]
+                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kvw.h"),
+                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kvw8.h")]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
                 "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 # per-source extras.  The split kernel keeps its fp32 arithmetic scalar: the SLP vectoriser would pair it into
@@ -141,8 +147,9 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        # one pool for all five libraries; the decode kernels are among the longest translation units, so they start first
+        # one pool for all six libraries; the decode kernels are among the longest translation units, so they start first
         kv8_futs = [ex.submit(_compile, s, force) for s in KV8_SOURCES]
+        kvw8_futs = {s: ex.submit(_compile, s, force) for s in KVW8_SOURCES if s not in KV8_SOURCES}
         kvw_futs = {s: ex.submit(_compile, s, force) for s in KVW_SOURCES if s not in KV_SOURCES}
         paged_futs = {s: ex.submit(_compile, s, force) for s in PAGED_SOURCES if s not in KV_SOURCES}
         kv_futs = [ex.submit(_compile, s, force) for s in KV_SOURCES]
@@ -151,6 +158,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
         paged_objs = [paged_futs[s].result() if s in paged_futs else kv_objs[KV_SOURCES.index(s)] for s in PAGED_SOURCES]
         kv8_objs = [f.result() for f in kv8_futs]
         kvw_objs = [kvw_futs[s].result() if s in kvw_futs else kv_objs[KV_SOURCES.index(s)] for s in KVW_SOURCES]
+        kvw8_objs = [kvw8_futs[s].result() if s in kvw8_futs else kv8_objs[KV8_SOURCES.index(s)] for s in KVW8_SOURCES]
         abl_objs = []
         if ablation:
             abl_objs = list(ex.map(lambda s: _compile(s, force, True), ABLATION_SOURCES + ABLATION_DEPENDENT))
@@ -160,6 +168,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
     _link(PAGED_LIB_PATH, paged_objs, force)
     _link(KV8_LIB_PATH, kv8_objs, force)
     _link(KVW_LIB_PATH, kvw_objs, force)
+    _link(KVW8_LIB_PATH, kvw8_objs, force)
     _build_driver(DRIVER_PATH, LIB_PATH, "flashattn_amd", force)
     if ablation:
         _link(ABL_LIB_PATH, abl_objs, force)
@@ -167,7 +176,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
     if torch_binding:
         build_torch_binding(force=force, verbose=verbose)
     if verbose:
-        print(f"built {LIB_PATH}, {KV_LIB_PATH}, {PAGED_LIB_PATH}, {KV8_LIB_PATH} and {KVW_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
+        print(f"built {LIB_PATH}, {KV_LIB_PATH}, {PAGED_LIB_PATH}, {KV8_LIB_PATH}, {KVW_LIB_PATH} and {KVW8_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
     return LIB_PATH
 
 

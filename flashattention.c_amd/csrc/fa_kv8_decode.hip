@@ -1,266 +1,20 @@
 // fa_kv8_decode.hip -- the decode kernel of libflashattn_amd_kv8.so: fa_kv_decode_core.h's workgroup, arithmetic, merge and page walk over a
-// cache of 8-bit floats (OCP e4m3fn, one byte per element), contiguous or paged, with a loop of its own.  No counterpart in the reference.
-//
-// Arithmetic -- the contract of include/flashattn_amd_kv8.h.  e4m3 -> bf16 is exact for every non-NaN code, so K and V are dequantised to
-// bf16 WITHOUT their scales and then meet the very instruction sequence of the 16-bit kernels.  k_scale arrives folded into the softmax scale
-// (host, one fp32 product); v_scale multiplies the normalised fp32 result once: here, before the store to o, in an unsplit launch; in
-// fa_kv8_combine.hip, behind the merge of the shares, in a split one.  With v_scale a power of two the result is, bit for bit, v_scale x what
-// the 16-bit kernels give on the cache dequantised to bf16.
-//
-// Data movement, per wave and 64-key block -- what differs from fa_kv_decode16_body.h:
-//   K  the A operand of K Q^T is "lane (key, half) holds 8 consecutive columns of its key per 16-column step": one 8-byte load at
-//      ks * 16 + hi * 8 (the 16-bit kernels: one 16-byte load).  The bytes stay in registers as they came and are converted
-//      (v_cvt_pk_f32_fp8, then the pack to bf16) in front of the matrix instruction that takes them.
-//   V  the second product contracts over keys and needs V^T fragments.  A lane loads 16 bytes = 16 columns of one key, converts them to
-//      32 bytes of bf16 and stores those into the V image of fa_bf16_common.h ([key/4][col/16][4][16] sub-tiles), which ds_read_b64_tr_b16
-//      reads as before.  Inside a 128-byte sub-tile the 16-byte slots are XOR-ed with the sub-tile's column block (v_swz): the eight
-//      consecutive lanes one ds_write_b128 group serves hold one or two keys across the column blocks, which would all fall on the same
-//      banks; a transposing read covers whole sub-tiles and stays conflict-free under any permutation inside them.
-// Every load is a register load: the compiler counts vmcnt itself.  The look-ahead is kept -- the bytes of block j + 1 (K and V, registers)
-// are in flight while block j is computed -- and the image is written and read by the same wave inside one step (LDS operations of a wave
-// execute in order), so one image per wave suffices: half the LDS of the 16-bit kernels and no barrier in the loop.
+// cache of 8-bit floats (OCP e4m3fn, one byte per element), contiguous or paged, with a loop of its own: fa_kv8_decode_body.h with
+// WINDOW = false, the same text the kernel of fa_kvw8_decode.hip compiles with WINDOW = true.  No counterpart in the reference.
 #include "fa_kv8.h"
-#include "fa_kv_decode_core.h"
+#include "fa_kv8_decode_core.h"
 
 namespace fa {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-template <int D>
-struct Kv8Cfg {
-    static constexpr int KS = D / 16, DB = D / 32;
-    static constexpr int LPR = D / 16;                     // lanes per V row: 16 bytes (16 columns) each
-    static constexpr int kVLoads = kKvBlk * D / 1024;      // 16-byte V loads per lane and block
-    static constexpr int kRowsPerLoad = kWave / LPR;       // keys one V load instruction covers
-    static constexpr int kVTile = kKvBlk * 2 * D;          // bytes of the V image (64 keys, bf16)
-    static constexpr int kMergeBytes = kKvRowTile * kKvMergeStride(D) * 4;
-    static constexpr int kWaveLds = kVTile > kMergeBytes ? kVTile : kMergeBytes;   // one image per wave, reused by the merge
-    static_assert(kPagedMinPage % kRowsPerLoad == 0, "a V load must not straddle a 16-key group");
-    static_assert(kWaveLds % 128 == 0, "sub-tile alignment");
-};
-
-// 8 e4m3 bytes (two dwords, ascending columns) -> 8 bf16, exactly
-__device__ __forceinline__ bf16x8 cvt_fp8x8(unsigned lo, unsigned hi)
-{
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
-    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
-    bf16x8 r;
-    r[0] = (__bf16)a[0], r[1] = (__bf16)a[1], r[2] = (__bf16)b[0], r[3] = (__bf16)b[1];
-    r[4] = (__bf16)c[0], r[5] = (__bf16)c[1], r[6] = (__bf16)d[0], r[7] = (__bf16)d[1];
-    return r;
-}
-
-// byte offset in the V image -> where it is kept: the 16-byte slot (bits 4 .. 6) XOR a code of the sub-tile's column block (see above)
-template <int D>
-__device__ __forceinline__ int v_swz(int off)
-{
-    constexpr int LPR = D / 16;
-    const int cb = (off >> 7) % LPR;
-    const int g = LPR == 8 ? cb : ((cb & 1) | ((cb & 2) << 1));
-    return off ^ (g << 4);
-}
 
 template <int D, bool CAUSAL, bool OUT_F32, bool PAGED>
 __global__ __launch_bounds__(kKvWaves* kWave) void fa_kv8_decode_kernel(Kv8Params p8)
 {
+    constexpr bool WINDOW = false;
+    constexpr int window_left = 0;   // never read
     const PagedParams& pp = p8.pg;
     const KvParams& p = pp.kv;
-    constexpr int NP = kPagedBlockPages;
-    using C = Kv8Cfg<D>;
-    constexpr int KS = C::KS, DB = C::DB, LPR = C::LPR, NV = C::kVLoads;
-    __shared__ __attribute__((aligned(1024))) char smem[kKvWaves * C::kWaveLds];
-    __shared__ float m_s[kKvWaves][kKvRowTile], l_s[kKvWaves][kKvRowTile];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lq = lane & 31, hi = lane >> 5;
-
-    const KvTile tl = kv_tile<CAUSAL>(p, PAGED ? pp.heads_kv : 1);
-    if (kv_share_is_empty(p, tl)) {
-        kv_mark_share_empty(p, tl);
-        return;
-    }
-    const bool row_ok = kv_row_ok(p, tl, lq);
-    const int lim = kv_last_visible_key<CAUSAL>(p, tl, lq);
-    const int slab = tl.slab, seq = tl.seq, head = tl.head, kbeg = tl.kbeg, kend = tl.kend, nblk = tl.nblk;
-
-    bf16x8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = kv_q_fragment<D>(p.q, tl.prow0, row_ok, lq, hi, ks);
-    bf16x8 ones;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-
-    // one byte per element: every offset below is in bytes
-    const uint8_t* kg = (const uint8_t*)p.k + (PAGED ? (int64_t)head * pp.head_stride : (int64_t)slab * p.kv_slab_stride);
-    const uint8_t* vg = (const uint8_t*)p.v + (PAGED ? (int64_t)head * pp.head_stride : (int64_t)slab * p.kv_slab_stride);
-    cst_i32_t* tbl = (cst_i32_t*)(pp.table + (int64_t)seq * pp.max_pages);
-    const int page_mask = (1 << pp.page_shift) - 1;
-    const unsigned row_stride = (unsigned)pp.row_stride;
-    char* vbuf = smem + wave * C::kWaveLds;
-    const int li = lane & 15;
-    // this lane's corner of a V^T fragment in the V image, per 32-column block (the swizzle depends on the column block, not on the key group)
-    int v_rd_off[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-        v_rd_off[db] = v_swz<D>((hi * (D / 16) + ((lane >> 4) & 1) + 2 * db) * 128 + (li >> 2) * 32 + (li & 3) * 8);
-    // ... and where this lane's 16 columns of a V load go: key lane / LPR of the load's rows, column block lane % LPR, as two 16-byte halves
-    const int v_key = lane / LPR, v_cb = lane % LPR;
-    const int v_wr_lo = v_swz<D>(((v_key / 4) * LPR + v_cb) * 128 + (v_key % 4) * 32);
-    const int v_wr_hi = v_swz<D>(((v_key / 4) * LPR + v_cb) * 128 + (v_key % 4) * 32 + 16);
-    const float c = p.scale_log2e;
-
-    f32x16 o[DB], lacc;
-    float m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) lacc[r] = 0.0f;
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-
-    // The bytes of one block: K as KS 8-byte pieces for each of the lane's two keys, V as NV 16-byte pieces.  pb: its page offsets (PAGED)
-    auto load_block = [&](int kv0, const int64_t(&pb)[NP], u32x2(&kf)[2][KS], u32x4(&vf)[NV]) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const int row = min(kv0 + kb * 32 + lq, kend - 1);
-            const uint8_t* kr;
-            if constexpr (PAGED)
-                kr = kg + page_of_k_row(pb, kb, lq) + (unsigned)(row & page_mask) * row_stride + hi * 8;
-            else
-                kr = kg + (int64_t)row * D + hi * 8;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) kf[kb][ks] = *(const u32x2*)(kr + ks * 16);
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int row = min(kv0 + i * C::kRowsPerLoad + v_key, kend - 1);
-            const uint8_t* vr;
-            if constexpr (PAGED)   // the 16-key group of a piece is the same in every lane
-                vr = vg + pb[i * C::kRowsPerLoad / kPagedMinPage] + (unsigned)(row & page_mask) * row_stride + v_cb * 16;
-            else
-                vr = vg + (int64_t)row * D + v_cb * 16;
-            vf[i] = *(const u32x4*)vr;
-        }
-    };
-
-    // One block.  The K and V bytes ping-pong between two register sets by NAME (the loop below is unrolled by two): a copy "current = next"
-    // at the end of a step would have to wait for the next block's loads.
-    // PAGED: the table runs two blocks ahead of the loads: pg[] holds the page offsets of the block whose loads the next step issues, ent[]
-    // the entries of the block after that, in flight from the end of one step to the end of the next.
-    int64_t pg[NP];
-    int ent[NP];
-    auto step = [&](int blk, const u32x2(&kcur)[2][KS], const u32x4(&vcur)[NV], u32x2(&knext)[2][KS], u32x4(&vnext)[NV]) __attribute__((always_inline)) {
-        const int kv0 = kbeg + blk * kKvBlk;
-        // The wave's next block, unconditionally.  Past the share's end every lane's row is redirected to the share's last row (one cached
-        // row per load), so the last step costs no traffic and the loop body has no branch.
-        load_block(kv0 + kKvWaves * kKvBlk, pg, knext, vnext);
-        // The loads stay HERE: their values are first used in the next step, which for every second step sits behind the loop's `if`, and
-        // without this statement the compiler sinks them down to that use -- nothing would be in flight while this block is computed.
-        asm volatile("" ::: "memory");
-
-        f32x16 s[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                u32x2 kk = kcur[kb][ks];
-                asm volatile("" : "+v"(kk));   // ... and this block's products stay BEHIND them: hoisted above, they would be waited for with nothing new in flight
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cvt_fp8x8(kk[0], kk[1]), qf[ks], s[kb], 0, 0, 0);
-            }
-
-        // this block's V: bf16 into the image (the previous step's reads of it were issued before these stores: LDS runs in order)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            char* dst = vbuf + i * (kWave * 32);   // kRowsPerLoad keys = kRowsPerLoad / 4 key groups of LPR sub-tiles: 2 KiB per load
-            *(bf16x8*)(dst + v_wr_lo) = cvt_fp8x8(vcur[i][0], vcur[i][1]);
-            *(bf16x8*)(dst + v_wr_hi) = cvt_fp8x8(vcur[i][2], vcur[i][3]);
-        }
-
-        bf16x8 ph[4], pl[4];
-        // kv_mask_and_max (fa_kv_decode_core.h) written out: called as a function here, hipcc moves four of this file's sixteen kernels off
-        // their recorded instruction profile (two VGPRs more, other vmcnt waits), and tests/test_kv_code_profile.py holds them to it
-        const int rel = lim - kv0 - 4 * hi;   // key offset (kb * 32 + (r & 3) + 8 * (r >> 2)) > rel: not visible
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float t = (kb * 32 + (r & 3) + 8 * (r >> 2) > rel) ? -INFINITY : s[kb][r] * c;
-                s[kb][r] = t;
-                mx = fmaxf(mx, t);
-            }
-        mx = xhalf_max(mx);
-        const float m_new = fmaxf(m, mx);
-        const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;   // a row that has seen no key yet: p = 0, no NaN
-        const float alpha = fast_exp2(m - m_use);
-        m = m_new;
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lacc[r] *= alpha;
-        kv_p_terms(s, m_use, ph, pl);
-
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int f = kb * 2 + t;
-#pragma unroll
-                for (int db = 0; db < DB; ++db) {
-                    const char* src = vbuf + v_rd_off[db];
-                    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(src + (kb * 8 + 4 * t + 0) * (D / 16) * 128));
-                    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(src + (kb * 8 + 4 * t + 2) * (D / 16) * 128));
-                    const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph[f], o[db], 0, 0, 0);
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pl[f], o[db], 0, 0, 0);
-                }
-                lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, ph[f], lacc, 0, 0, 0);
-                lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pl[f], lacc, 0, 0, 0);
-            }
-        if constexpr (PAGED) {
-            // The step's matrix instructions are issued before the table is touched: lgkmcnt counts scalar loads and LDS reads together, so a
-            // product scheduled behind the fetch below would wait for a table round trip together with its V^T fragment (measured with pages
-            // of 16 rows, where every step touches a new line of the table: 1.26-1.29 x the contiguous cache before this, docs/kv_fp8.md).
-#pragma unroll
-            for (int db = 0; db < DB; ++db) asm volatile("" : "+v"(o[db]));
-            asm volatile("" : "+v"(lacc));
-            pages_landed(ent, pp.page_stride, pg);                                        // the block the next step issues: fetched a step ago
-            fetch_pages(tbl, pp.page_shift, kv0 + 3 * kKvWaves * kKvBlk, kend, ent);      // the block after that
-        }
-    };
-
-    u32x2 ka[2][KS], kb_[2][KS];
-    u32x4 va[NV], vb[NV];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) pg[i] = 0, ent[i] = 0;
-    if (wave < nblk) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
-        if constexpr (PAGED) {
-            int e0[NP], e1[NP];
-            fetch_pages(tbl, pp.page_shift, kbeg + wave * kKvBlk, kend, e0);
-            fetch_pages(tbl, pp.page_shift, kbeg + (wave + kKvWaves) * kKvBlk, kend, e1);
-            int64_t p0[NP];
-            pages_landed(e0, pp.page_stride, p0);
-            load_block(kbeg + wave * kKvBlk, p0, ka, va);
-            pages_landed(e1, pp.page_stride, pg);
-            fetch_pages(tbl, pp.page_shift, kbeg + (wave + 2 * kKvWaves) * kKvBlk, kend, ent);
-        } else {
-            load_block(kbeg + wave * kKvBlk, pg, ka, va);
-        }
-    }
-    for (int blk = wave; blk < nblk; blk += 2 * kKvWaves) {
-        step(blk, ka, va, kb_, vb);
-        if (blk + kKvWaves < nblk) step(blk + kKvWaves, kb_, vb, ka, va);
-    }
-
-    mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight; the image's last reads have been consumed
-    kv_merge_and_store<D, OUT_F32, true, C::kWaveLds>(p, tl, smem, m_s, l_s, wave, lq, hi, m, o, lacc, p8.v_scale);
+    const float& v_scale = p8.v_scale;
+#include "fa_kv8_decode_body.h"
 }
 
 template <int D, bool PAGED>

@@ -1,5 +1,5 @@
 // fa_kv8_host.cpp -- the entry points of include/flashattn_amd_kv8.h over fa_kv_host.h (validation, plan, launch parameters) with an element of
-// ONE byte, and the library's own checks: the two scales of the cache.
+// ONE byte and the two scales of the cache (check_scales).
 #include "fa_kv8.h"
 #include "fa_kv_host.h"
 #include "flashattn_amd_kv8.h"
@@ -9,18 +9,6 @@ namespace fa {
 static thread_local KvError g_kv8_error;
 static const KvWords kKv8Words = {1, "bh_kv (batch, heads_kv)", "q and o are as in fa_kv_forward", "bh_kv * group (batch * heads_kv * group)", "fa_kv8_workspace_bytes",
                                   "k8", "v8", "q, k8, v8, o"};
-
-// scale' = fp32(scale * k_scale), the ONE product the contract names; v_scale
-static int check_scales(KvError& e, float scale, float k_scale, float v_scale, float* folded)
-{
-    if (!std::isfinite(k_scale) || !(k_scale > 0.0f)) return e.fail(FA_ERR_INVALID_ARGUMENT, "k_scale must be finite and > 0");
-    if (!std::isfinite(v_scale) || !(v_scale > 0.0f)) return e.fail(FA_ERR_INVALID_ARGUMENT, "v_scale must be finite and > 0");
-    if (const int rc = check_scale(e, scale)) return rc;
-    const volatile float prod = scale * k_scale;   // volatile: rounded to fp32 here, whatever the host compiler's excess precision
-    if (!std::isfinite(prod) || prod == 0.0f) return e.fail(FA_ERR_INVALID_ARGUMENT, "scale * k_scale must be finite and non-zero in fp32");
-    *folded = prod;
-    return FA_OK;
-}
 
 static int run(KvError& e, Kv8Params& p8, int32_t d, float v_scale, int32_t causal, int out_f32, int paged, void* stream)
 {

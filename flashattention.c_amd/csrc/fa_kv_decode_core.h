@@ -1,7 +1,7 @@
 // fa_kv_decode_core.h -- the device pieces the decode kernels of the KV-cache libraries are made of: few query rows against many cached
 // keys (decode, chunked prefill, cross-attention, GQA), the bandwidth-bound twin of the square kernels.  No counterpart in the reference, whose
 // one entry computes square self-attention.  Users: fa_kv_decode16_body.h (the 16-bit loop of fa_kv_decode.hip, fa_paged_decode.hip and, with
-// WINDOW = true, fa_kvw_decode.hip) and fa_kv8_decode.hip.  Every piece is forced inline; nothing here branches at run time on the kind of
+// WINDOW = true, fa_kvw_decode.hip) and fa_kv8_decode_body.h (the fp8 loop of fa_kv8_decode.hip and, with WINDOW = true, fa_kvw8_decode.hip).  Every piece is forced inline; nothing here branches at run time on the kind of
 // cache, and what a sliding window adds sits behind `if constexpr (WINDOW)`: with WINDOW = false (the default of every piece) the text is
 // what it was.
 //

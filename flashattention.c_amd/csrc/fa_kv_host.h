@@ -1,10 +1,11 @@
-// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp): argument validation
+// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp, fa_kvw8_host.cpp): argument validation
 // (no device is touched before it passes; lengths and block tables are device memory and never dereferenced here), the workspace and the
 // plan it selects, and the fill of the launch parameters.  Inline, like kv_plan: the libraries link no host object of each other.  The plan
 // is fa_kv.h's kv_plan over bh_kv = batch * heads_kv, so splits, share and workspace are the same in all of them for the same shapes (the windowed library: for the same span).
 // Each library keeps its entry points, its version string and its own thread-local error text (KvError), and passes in the few words in
 // which its messages differ (KvWords).  tests/test_kv_host_errors.py holds every check to its code and its text.
 #pragma once
+#include "fa_kvw.h"
 #include "fa_paged.h"
 #include "flashattn_amd_paged.h"
 
@@ -83,6 +84,26 @@ inline int check_page_size(KvError& e, int32_t page_size)
 inline int check_scale(KvError& e, float scale)
 {
     if (!std::isfinite(scale) || scale == 0.0f) return e.fail(FA_ERR_INVALID_ARGUMENT, "scale must be finite and non-zero");
+    return FA_OK;
+}
+
+// the two scales of an fp8 cache (the libraries of fa_kv8.h and fa_kvw8.h): scale' = fp32(scale * k_scale), the ONE product the contract names; v_scale
+inline int check_scales(KvError& e, float scale, float k_scale, float v_scale, float* folded)
+{
+    if (!std::isfinite(k_scale) || !(k_scale > 0.0f)) return e.fail(FA_ERR_INVALID_ARGUMENT, "k_scale must be finite and > 0");
+    if (!std::isfinite(v_scale) || !(v_scale > 0.0f)) return e.fail(FA_ERR_INVALID_ARGUMENT, "v_scale must be finite and > 0");
+    if (const int rc = check_scale(e, scale)) return rc;
+    const volatile float prod = scale * k_scale;   // volatile: rounded to fp32 here, whatever the host compiler's excess precision
+    if (!std::isfinite(prod) || prod == 0.0f) return e.fail(FA_ERR_INVALID_ARGUMENT, "scale * k_scale must be finite and non-zero in fp32");
+    *folded = prod;
+    return FA_OK;
+}
+
+// the window of a call (the libraries of fa_kvw.h and fa_kvw8.h): rejected below 0, saturated at 2^24 (no cache is longer)
+inline int check_window(KvError& e, int32_t window_left, int32_t* w)
+{
+    if (window_left < 0) return e.fail(FA_ERR_INVALID_ARGUMENT, "window_left = %d must be >= 0", window_left);
+    *w = window_left < kKvwMaxWindow ? window_left : kKvwMaxWindow;
     return FA_OK;
 }
 

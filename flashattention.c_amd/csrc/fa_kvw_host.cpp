@@ -10,14 +10,6 @@ static thread_local KvError g_kvw_error;
 static const KvWords kKvwWords = {2, "bh_kv", "caches are 16-bit", "bh_kv * group", "fa_kvw_workspace_bytes", "k", "v", "q, k, v, o"};
 static const KvWords kKvwPagedWords = {2, "batch, heads_kv", "caches are 16-bit", "batch * heads_kv * group", "fa_kvw_paged_workspace_bytes", "k", "v", "q, k, v, o"};
 
-// the window of a call: rejected below 0, saturated at 2^24 (no cache is longer)
-static int check_window(KvError& e, int32_t window_left, int32_t* w)
-{
-    if (window_left < 0) return e.fail(FA_ERR_INVALID_ARGUMENT, "window_left = %d must be >= 0", window_left);
-    *w = window_left < kKvwMaxWindow ? window_left : kKvwMaxWindow;
-    return FA_OK;
-}
-
 // shape and window of a query (no pointers): the plan of the call, or nothing
 static bool plan_query(const KvWords& words, int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t dtype,
                        int32_t window_left, KvPlan* pl)

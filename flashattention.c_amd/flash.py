@@ -23,7 +23,7 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kvw, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -389,7 +389,8 @@ def _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need):
 
 def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
                    kv_len: Optional[int] = None, kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False,
-                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None):
+                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, workspace: Optional[torch.Tensor] = None,
+                   window_left: Optional[int] = None):
     """``forward_kv`` over a cache of 8-bit floats (``include/flashattn_amd_kv8.h``): half the K/V bytes of a call.
 
     ``q`` is bfloat16 ``(BHq, nq, d)``; ``k8``, ``v8`` are ``torch.float8_e4m3fn`` ``(BHkv, capacity, d)`` (a ``torch.uint8`` tensor is rejected:
@@ -398,8 +399,14 @@ def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
     one fp32 product, ``v_scale`` multiplies the normalised result once, the LSE is that of the scaled scores.  With ``v_scale`` a power of two
     the result is bit for bit ``v_scale * forward_kv(q, k8.to(bfloat16), v8.to(bfloat16), scale=fp32(scale * k_scale))``.  Everything else --
     ``kv_len``, ``kv_lens``, ``causal``, rows without keys, ``d``, output dtypes -- is ``forward_kv``'s; scratch has the size ``workspace_bytes_kv``
-    gives for the same shapes.
+    gives for the same shapes and ``window_left``.
+
+    ``window_left`` (``include/flashattn_amd_kvw8.h``; ``None``: no window) is ``forward_kv``'s sliding window with its rules: an ``int >= 0``
+    (negative raises ``ValueError``), only the keys of the window are walked, and with ``lo = max(0, len - nq - window_left)`` no cache byte of a
+    row below ``lo`` or at or beyond ``len`` is read -- such rows may hold anything, the NaN codes included.  With ``v_scale`` a power of two the
+    result is bit for bit ``v_scale *`` that of ``forward_kv`` on the dequantised cache with the same ``window_left``.
     """
+    window_left = _window(window_left)
     for name, t in (("q", q), ("k8", k8), ("v8", v8)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
@@ -428,33 +435,43 @@ def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
         if kv_lens.dtype != torch.int32 or kv_lens.shape != (bhkv,) or kv_lens.device != q.device or not kv_lens.is_contiguous():
             raise ValueError(f"kv_lens must be a contiguous torch.int32 tensor of shape ({bhkv},) on {q.device}")
     q, k8, v8 = q.contiguous(), k8.contiguous(), v8.contiguous()
-    L = _cabi_kv8.lib()
+    L = _cabi_kv8.lib() if window_left is None else _cabi_kvw8.lib()
     with torch.cuda.device(q.device):
         odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
         dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
-        need = int(L.fa_kv8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        if window_left is None:
+            need = int(L.fa_kv8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
+        else:
+            need = int(L.fa_kvw8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt, window_left))
         out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
         stream = torch.cuda.current_stream().cuda_stream
-        rc = L.fa_kv8_forward(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                              bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
-                              d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt,
-                              workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                              workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-    _cabi_kv8.check(rc)
+        head = (q.data_ptr(), k8.data_ptr(), v8.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
+                d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt)
+        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+        rc = L.fa_kv8_forward(*head, *tail) if window_left is None else L.fa_kvw8_forward(*head, window_left, *tail)
+    (_cabi_kv8 if window_left is None else _cabi_kvw8).check(rc)
     return (out, lse) if return_lse else out
 
 
 def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
                       k_scale: float = 1.0, v_scale: float = 1.0, seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None,
                       scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
-                      workspace: Optional[torch.Tensor] = None):
+                      workspace: Optional[torch.Tensor] = None, window_left: Optional[int] = None):
     """``forward_paged`` over pools of 8-bit floats (``include/flashattn_amd_kv8.h``); scales and arithmetic as in ``forward_kv_fp8``.
 
     ``k_pool8``, ``v_pool8`` are ``torch.float8_e4m3fn`` ``(pages, page, d)`` or ``(pages, page, H, d)`` (``torch.uint8`` is rejected: ``.view`` it).
     Their strides are taken as they are and a pool is never copied: a last stride other than 1 or a stride that is not a multiple of 16
     elements (16 bytes) raises.  Block table, ``seq_lens``, ``kv_len``, page sizes and everything else are ``forward_paged``'s, and the result is
-    ``forward_kv_fp8``'s, bit for bit, on the gathered bytes; scratch has the size ``workspace_bytes_paged`` gives for the same shapes.
+    ``forward_kv_fp8``'s, bit for bit, on the gathered bytes; scratch has the size ``workspace_bytes_paged`` gives for the same shapes and
+    ``window_left``.
+
+    ``window_left`` (``include/flashattn_amd_kvw8.h``; ``None``: no window) is ``forward_paged``'s sliding window: with
+    ``lo = max(0, len - nq - window_left)`` no pool byte of a key below ``lo`` or at or beyond ``len`` is read, and no table entry below
+    ``lo // page`` or at or beyond ``ceil(len / page)``: pages that have slid out can be freed or reused and may hold NaN codes.
     """
+    window_left = _window(window_left)
     for name, t in (("q", q), ("k_pool8", k_pool8), ("v_pool8", v_pool8), ("block_table", block_table)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
@@ -500,18 +517,22 @@ def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
     q = q.contiguous()
     cache = _cabi_kv8.FaPagedCache(k_pool8.data_ptr(), v_pool8.data_ptr(), pages, page, page_stride, row_stride, head_stride,
                                    block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
-    L = _cabi_kv8.lib()
+    L = _cabi_kv8.lib() if window_left is None else _cabi_kvw8.lib()
     with torch.cuda.device(q.device):
         odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
         dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
-        need = int(L.fa_kv8_workspace_bytes(batch * heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        if window_left is None:
+            need = int(L.fa_kv8_workspace_bytes(batch * heads_kv, group, nq, nk, d, int(bool(causal)), dt))
+        else:
+            need = int(L.fa_kvw8_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt, window_left))
         out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
         stream = torch.cuda.current_stream().cuda_stream
-        rc = L.fa_kv8_paged_forward(q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                                    batch, heads_kv, group, nq, nk, d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt,
-                                    workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                                    workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-    _cabi_kv8.check(rc)
+        head = (q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
+                batch, heads_kv, group, nq, nk, d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt)
+        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+        rc = L.fa_kv8_paged_forward(*head, *tail) if window_left is None else L.fa_kvw8_paged_forward(*head, window_left, *tail)
+    (_cabi_kv8 if window_left is None else _cabi_kvw8).check(rc)
     return (out, lse) if return_lse else out
 
 

@@ -42,8 +42,8 @@
  *             cache of `span` keys.  They depend on the shapes and on window_left only, never on lengths.  NULL or 0 bytes: the
  *             call runs unsplit.  Non-NULL but too small: FA_ERR_INVALID_ARGUMENT.  Contents need no initialisation.
  *
- * Out of scope: fp8 caches (include/flashattn_amd_kv8.h; their decode loop is a different one), attention sinks, a right window
- * other than causal / unbounded, soft-capping.
+ * Out of scope: attention sinks, a right window other than causal / unbounded, soft-capping.  fp8 caches under a window:
+ * include/flashattn_amd_kvw8.h (libflashattn_amd_kvw8.so; their decode loop is a different one).
  */
 #ifndef FLASHATTN_AMD_KVW_H
 #define FLASHATTN_AMD_KVW_H
