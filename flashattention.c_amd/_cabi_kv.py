@@ -1,54 +1,10 @@
 """ctypes view of include/flashattn_amd_kv.h (the KV-cache attention extension, libflashattn_amd_kv.so; this file only binds it)."""
 from __future__ import annotations
 
-import ctypes
-import os
-
 from ._cabi import FA_DTYPE_BF16, FA_DTYPE_BF16_OUT_F32, FA_DTYPE_F32, FA_OK, ExtensionMissing, FlashAttnError  # noqa: F401
+from ._cabi_ext import SHAPE, Extension, c_int, forward_args, i32, i64, queries, vp
 
-PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv.so")
-
-# every symbol include/flashattn_amd_kv.h declares
-EXPORTED_SYMBOLS = (
-    "fa_kv_workspace_bytes", "fa_kv_splits_for", "fa_kv_forward", "fa_kv_stream_read", "fa_kv_kernel_name_for", "fa_kv_last_error", "fa_kv_version",
-)
-
-_libs = {}
-
-
-def bind(path: str) -> ctypes.CDLL:
-    """Load a build of the extension and declare its prototypes (profiles/kv_decode.py binds measurement builds beside the product)."""
-    L = ctypes.CDLL(path)
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    shape = [i64, i32, i64, i64, i32, i32, i32]   # bh_kv, group, nq, nk, d, causal, dtype
-    L.fa_kv_workspace_bytes.argtypes = shape
-    L.fa_kv_workspace_bytes.restype = ctypes.c_size_t
-    L.fa_kv_splits_for.argtypes = shape
-    L.fa_kv_splits_for.restype = i32
-    L.fa_kv_forward.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i64, i64, vp, i32, f32, i32, i32, vp, ctypes.c_size_t, vp]
-    L.fa_kv_forward.restype = ctypes.c_int
-    L.fa_kv_stream_read.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp]
-    L.fa_kv_stream_read.restype = ctypes.c_int
-    L.fa_kv_kernel_name_for.argtypes = shape
-    L.fa_kv_kernel_name_for.restype = ctypes.c_char_p
-    L.fa_kv_last_error.argtypes = []
-    L.fa_kv_last_error.restype = ctypes.c_char_p
-    L.fa_kv_version.argtypes = []
-    L.fa_kv_version.restype = ctypes.c_char_p
-    return L
-
-
-def lib(path: str = LIB_PATH) -> ctypes.CDLL:
-    if path not in _libs:
-        if not os.path.exists(path):
-            raise ExtensionMissing(
-                f"{path} not found. Build it with `python flashattention.c_amd/build.py` "
-                "(or __graft_entry__.build()). There is no CPU/PyTorch fallback for this operator.")
-        _libs[path] = bind(path)
-    return _libs[path]
-
-
-def check(code: int) -> None:
-    if code != FA_OK:
-        raise FlashAttnError(code, lib().fa_kv_last_error().decode("utf-8", "replace"))
+# every symbol include/flashattn_amd_kv.h declares, in its order
+_q = queries(SHAPE, SHAPE)
+_ext = Extension("kv", _q[:2] + [("forward", forward_args(), c_int), ("stream_read", [vp, vp, i64, i64, i64, i32, vp, vp], c_int)] + _q[2:])
+LIB_PATH, EXPORTED_SYMBOLS, bind, lib, check = _ext.LIB_PATH, _ext.EXPORTED_SYMBOLS, _ext.bind, _ext.lib, _ext.check

@@ -1,60 +1,9 @@
 """ctypes view of include/flashattn_amd_paged.h (paged KV-cache attention, libflashattn_amd_paged.so; this file only binds it)."""
 from __future__ import annotations
 
-import ctypes
-import os
-
 from ._cabi import FA_DTYPE_BF16, FA_DTYPE_BF16_OUT_F32, FA_DTYPE_F32, FA_OK, ExtensionMissing, FlashAttnError  # noqa: F401
+from ._cabi_ext import PAGE_SIZE, PAGED_SHAPE, Extension, FaPagedCache, c_int, forward_args, queries  # noqa: F401
 
-PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_paged.so")
-
-# every symbol include/flashattn_amd_paged.h declares
-EXPORTED_SYMBOLS = (
-    "fa_paged_workspace_bytes", "fa_paged_splits_for", "fa_paged_kernel_name_for", "fa_paged_forward", "fa_paged_last_error", "fa_paged_version",
-)
-
-
-class FaPagedCache(ctypes.Structure):
-    """``fa_paged_cache``: the pools, their strides (elements), the block table and the lengths (device pointers)."""
-    _fields_ = [("k_pool", ctypes.c_void_p), ("v_pool", ctypes.c_void_p), ("num_pages", ctypes.c_int64), ("page_size", ctypes.c_int32),
-                ("page_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64),
-                ("block_table", ctypes.c_void_p), ("max_pages", ctypes.c_int32), ("seq_lens", ctypes.c_void_p)]
-
-
-_libs = {}
-
-
-def bind(path: str) -> ctypes.CDLL:
-    """Load a build of the library and declare its prototypes."""
-    L = ctypes.CDLL(path)
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    shape = [i64, i32, i32, i64, i64, i32, i32, i32]   # batch, heads_kv, group, nq, nk, d, causal, dtype
-    L.fa_paged_workspace_bytes.argtypes = shape
-    L.fa_paged_workspace_bytes.restype = ctypes.c_size_t
-    L.fa_paged_splits_for.argtypes = shape
-    L.fa_paged_splits_for.restype = i32
-    L.fa_paged_kernel_name_for.argtypes = shape + [i32]
-    L.fa_paged_kernel_name_for.restype = ctypes.c_char_p
-    L.fa_paged_forward.argtypes = [vp, ctypes.POINTER(FaPagedCache), vp, vp, i64, i32, i32, i64, i64, i32, f32, i32, i32, vp, ctypes.c_size_t, vp]
-    L.fa_paged_forward.restype = ctypes.c_int
-    L.fa_paged_last_error.argtypes = []
-    L.fa_paged_last_error.restype = ctypes.c_char_p
-    L.fa_paged_version.argtypes = []
-    L.fa_paged_version.restype = ctypes.c_char_p
-    return L
-
-
-def lib(path: str = LIB_PATH) -> ctypes.CDLL:
-    if path not in _libs:
-        if not os.path.exists(path):
-            raise ExtensionMissing(
-                f"{path} not found. Build it with `python flashattention.c_amd/build.py` "
-                "(or __graft_entry__.build()). There is no CPU/PyTorch fallback for this operator.")
-        _libs[path] = bind(path)
-    return _libs[path]
-
-
-def check(code: int) -> None:
-    if code != FA_OK:
-        raise FlashAttnError(code, lib().fa_paged_last_error().decode("utf-8", "replace"))
+# every symbol include/flashattn_amd_paged.h declares, in its order
+_ext = Extension("paged", queries(PAGED_SHAPE, PAGED_SHAPE + PAGE_SIZE) + [("forward", forward_args(paged=True), c_int)])
+LIB_PATH, EXPORTED_SYMBOLS, bind, lib, check = _ext.LIB_PATH, _ext.EXPORTED_SYMBOLS, _ext.bind, _ext.lib, _ext.check

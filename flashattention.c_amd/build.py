@@ -8,11 +8,8 @@ hipcc cross-compiles for gfx950 without a GPU present.
 
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
-``libflashattn_amd_kv.so`` (the KV-cache attention extension, include/flashattn_amd_kv.h; ``KV_SOURCES``) is always built beside it.
-``libflashattn_amd_paged.so`` (paged KV-cache attention, include/flashattn_amd_paged.h; ``PAGED_SOURCES``) likewise.
-``libflashattn_amd_kv8.so`` (both over an fp8 e4m3 cache, include/flashattn_amd_kv8.h; ``KV8_SOURCES``) likewise.
-``libflashattn_amd_kvw.so`` (both 16-bit caches under a sliding window, include/flashattn_amd_kvw.h; ``KVW_SOURCES``) likewise.
-``libflashattn_amd_kvw8.so`` (the fp8 caches under a sliding window, include/flashattn_amd_kvw8.h; ``KVW8_SOURCES``) likewise.
+The five KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
+sources) are always built beside it.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
 They are NOT part of the product library: its ``fa_forward_ex`` rejects their variant numbers.
@@ -60,34 +57,31 @@ ABLATION_SOURCES = ["experiments/" + f for f in (
 ABLATION_DEPENDENT = ["fa_fwd_bf16.hip", "fa_fwd_bf16_x4.hip", "fa_fwd_bf16_pipelined.hip", "fa_fwd_bf16_x2.hip", "fa_plan.cpp", "fa_counters.cpp", "fa_launch.cpp", "fa_api.cpp",
                       "fa_split_f32_d32.hip", "fa_split_f32_d64.hip"]
 ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
-# libflashattn_amd_kv.so, the KV-cache attention extension behind include/flashattn_amd_kv.h: a library of its own (ABI 6 of the product
-# library is frozen), self-contained -- it shares headers with the product, no object.  Longest translation unit first.
-KV_SOURCES = ["fa_kv_decode.hip", "fa_kv_combine.hip", "fa_kv_plan.cpp"]
-KV_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv.so")
-# libflashattn_amd_paged.so, the paged twin behind include/flashattn_amd_paged.h: its own decode kernel and host side, and the OBJECT of the KV library's
-# merge kernel (fa_kv_combine.hip is compiled once).  It exports no fa_kv_* symbol: the plan it shares is inline in csrc/fa_kv.h.
-PAGED_SOURCES = ["fa_paged_decode.hip", "fa_kv_combine.hip", "fa_paged_host.cpp"]
-PAGED_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_paged.so")
-# libflashattn_amd_kv8.so, both of them over an fp8 (e4m3fn) cache behind include/flashattn_amd_kv8.h: one decode kernel template, a merge kernel
-# that applies v_scale, its host side.  Self-contained like the KV library; it exports no fa_kv_* or fa_paged_* symbol.
-KV8_SOURCES = ["fa_kv8_decode.hip", "fa_kv8_combine.hip", "fa_kv8_host.cpp"]
-KV8_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kv8.so")
-# libflashattn_amd_kvw.so, sliding-window attention over the contiguous and the paged 16-bit cache behind include/flashattn_amd_kvw.h: its own
-# instances of the 16-bit decode loop (WINDOW = true), its host side, and the OBJECT of the KV library's merge kernel, like the paged library.
-KVW_SOURCES = ["fa_kvw_decode.hip", "fa_kv_combine.hip", "fa_kvw_host.cpp"]
-KVW_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kvw.so")
-# libflashattn_amd_kvw8.so, sliding-window attention over the contiguous and the paged fp8 cache behind include/flashattn_amd_kvw8.h: its own
-# instances of the fp8 decode loop (WINDOW = true), its host side, and the OBJECT of the fp8 library's merge kernel (fa_kv8_combine.hip is compiled once).
-KVW8_SOURCES = ["fa_kvw8_decode.hip", "fa_kv8_combine.hip", "fa_kvw8_host.cpp"]
-KVW8_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_kvw8.so")
+# The KV-cache extension libraries: tag -> sources of libflashattn_amd_<tag>.so behind include/flashattn_amd_<tag>.h.  Each is a library of its own
+# (ABI 6 of the product library is frozen) that shares headers with the product and no object; within a library the longest translation unit
+# comes first, and the thread pool starts the libraries in this order, so the decode kernels, among the longest units of the whole build, start
+# first.  A source named by several libraries (SHARED_OBJECTS: the 16-bit merge kernel, and the fp8 one that applies v_scale) is compiled once, in
+# the turn of the library it belongs to, and its OBJECT is linked into each.  No library exports a symbol of another: what else they share (plan,
+# decode loop, validator) is inline in csrc/fa_kv*.h.
+EXT_LIBS = {
+    "kv8": ["fa_kv8_decode.hip", "fa_kv8_combine.hip", "fa_kv8_host.cpp"],      # contiguous and paged over an fp8 (e4m3fn) cache: one decode kernel template
+    "kvw8": ["fa_kvw8_decode.hip", "fa_kv8_combine.hip", "fa_kvw8_host.cpp"],   # the fp8 decode loop under a sliding window (WINDOW = true)
+    "kvw": ["fa_kvw_decode.hip", "fa_kv_combine.hip", "fa_kvw_host.cpp"],       # the 16-bit decode loop under a sliding window, contiguous and paged
+    "paged": ["fa_paged_decode.hip", "fa_kv_combine.hip", "fa_paged_host.cpp"],  # the paged twin of kv: its own decode kernel and host side
+    "kv": ["fa_kv_decode.hip", "fa_kv_combine.hip", "fa_kv_plan.cpp"],          # the KV-cache attention extension (16-bit contiguous cache)
+}
+SHARED_OBJECTS = {"fa_kv_combine.hip": "kv", "fa_kv8_combine.hip": "kv8"}
+KV_SOURCES = EXT_LIBS["kv"]
+
+
+def ext_lib_path(tag: str) -> str:
+    return os.path.join(PKG_DIR, f"libflashattn_amd_{tag}.so")
+
+
 ABL_DRIVER_PATH = os.path.join(PKG_DIR, "fa_driver_ablation")
 # every header under csrc/ (globbed: a new header cannot be forgotten -- ADVICE r04) plus the C ABI
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [os.path.join(ROOT, "include", "flashattn_amd.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kv.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_paged.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kv8.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kvw.h"),
-                                                                                                                            os.path.join(ROOT, "include", "flashattn_amd_kvw8.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))) + [
+    os.path.join(ROOT, "include", h) for h in ["flashattn_amd.h"] + [f"flashattn_amd_{tag}.h" for tag in sorted(EXT_LIBS)]]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
                 "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 # per-source extras.  The split kernel keeps its fp32 arithmetic scalar: the SLP vectoriser would pair it into
@@ -147,28 +141,17 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        # one pool for all six libraries; the decode kernels are among the longest translation units, so they start first
-        kv8_futs = [ex.submit(_compile, s, force) for s in KV8_SOURCES]
-        kvw8_futs = {s: ex.submit(_compile, s, force) for s in KVW8_SOURCES if s not in KV8_SOURCES}
-        kvw_futs = {s: ex.submit(_compile, s, force) for s in KVW_SOURCES if s not in KV_SOURCES}
-        paged_futs = {s: ex.submit(_compile, s, force) for s in PAGED_SOURCES if s not in KV_SOURCES}
-        kv_futs = [ex.submit(_compile, s, force) for s in KV_SOURCES]
+        # one pool for all six libraries: the extension libraries' sources first (each distinct one once), then the product's
+        ext_futs = {s: ex.submit(_compile, s, force) for tag, srcs in EXT_LIBS.items() for s in srcs if SHARED_OBJECTS.get(s, tag) == tag}
         objs = list(ex.map(lambda s: _compile(s, force), LIB_SOURCES))
-        kv_objs = [f.result() for f in kv_futs]
-        paged_objs = [paged_futs[s].result() if s in paged_futs else kv_objs[KV_SOURCES.index(s)] for s in PAGED_SOURCES]
-        kv8_objs = [f.result() for f in kv8_futs]
-        kvw_objs = [kvw_futs[s].result() if s in kvw_futs else kv_objs[KV_SOURCES.index(s)] for s in KVW_SOURCES]
-        kvw8_objs = [kvw8_futs[s].result() if s in kvw8_futs else kv8_objs[KV8_SOURCES.index(s)] for s in KVW8_SOURCES]
+        ext_objs = {tag: [ext_futs[s].result() for s in srcs] for tag, srcs in EXT_LIBS.items()}
         abl_objs = []
         if ablation:
             abl_objs = list(ex.map(lambda s: _compile(s, force, True), ABLATION_SOURCES + ABLATION_DEPENDENT))
             abl_objs += [o for s_, o in zip(LIB_SOURCES, objs) if s_ not in ABLATION_DEPENDENT]
     _link(LIB_PATH, objs, force)
-    _link(KV_LIB_PATH, kv_objs, force)
-    _link(PAGED_LIB_PATH, paged_objs, force)
-    _link(KV8_LIB_PATH, kv8_objs, force)
-    _link(KVW_LIB_PATH, kvw_objs, force)
-    _link(KVW8_LIB_PATH, kvw8_objs, force)
+    for tag in EXT_LIBS:
+        _link(ext_lib_path(tag), ext_objs[tag], force)
     _build_driver(DRIVER_PATH, LIB_PATH, "flashattn_amd", force)
     if ablation:
         _link(ABL_LIB_PATH, abl_objs, force)
@@ -176,7 +159,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: b
     if torch_binding:
         build_torch_binding(force=force, verbose=verbose)
     if verbose:
-        print(f"built {LIB_PATH}, {KV_LIB_PATH}, {PAGED_LIB_PATH}, {KV8_LIB_PATH}, {KVW_LIB_PATH} and {KVW8_LIB_PATH}" + (f" and {ABL_LIB_PATH}" if ablation else ""))
+        print("built " + ", ".join([LIB_PATH] + [ext_lib_path(tag) for tag in EXT_LIBS] + ([ABL_LIB_PATH] if ablation else [])))
     return LIB_PATH
 
 

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import ctypes
 from types import SimpleNamespace
-from typing import Optional, Tuple, Union
+from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -67,6 +67,15 @@ def _check_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> Tuple[int, 
     return bh, n, d
 
 
+def _workspace(workspace: Optional[torch.Tensor], need: int, device) -> Optional[torch.Tensor]:
+    """the caller's scratch if it will do, else ``need`` bytes from torch's caching allocator (256-byte aligned: its blocks are 512-byte multiples)"""
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=device) if need else None
+    if workspace.dtype != torch.uint8 or workspace.device != device or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {device}")
+    return workspace
+
+
 def forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *,
             scale: float = 1.0, return_lse: bool = False, kernel: Union[str, int] = "auto",
             out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
@@ -112,11 +121,7 @@ def forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = Fa
     L = _cabi.lib()
     with torch.cuda.device(q.device):
         need = int(L.fa_workspace_bytes(bh, n, d, int(bool(causal)), dt, kid))
-        if workspace is None:
-            # 256-byte aligned by the caching allocator (its blocks are 512-byte multiples)
-            workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
-        elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
-            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
+        workspace = _workspace(workspace, need, q.device)
         stream = torch.cuda.current_stream().cuda_stream
         rc = L.fa_forward_ws(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
                              lse.data_ptr() if lse is not None else None,
@@ -136,7 +141,204 @@ def workspace_bytes(bh: int, n: int, d: int, causal: bool = False, *, dtype: tor
     return int(_cabi.lib().fa_workspace_bytes(int(bh), int(n), int(d), int(bool(causal)), dt, _kernel_id(kernel)))
 
 
+
 KV_HEAD_DIMS = (64, 128)
+
+# ---- the four KV-cache entries: one front end.  What differs between a 16-bit and an fp8 cache is the _Family row, what differs between a contiguous
+# and a paged cache is the validator (_contiguous_cache / _paged_cache); library and symbols follow from (fp8?, paged?, window?) in _ENTRIES ----
+
+
+def _check_bf16_cache(fn: str, q, kn: str, k, vn: str, v, table=None) -> None:
+    """dtype and device checks of the two 16-bit entries: bf16 q and caches on one GPU, the block table with them."""
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError(f"q, {kn}, {vn} must share one dtype")
+    if q.dtype != torch.bfloat16:
+        raise TypeError(f"dtype {q.dtype} not supported by {fn} (bfloat16: caches are 16-bit)")
+    if table is None:
+        if not (q.is_cuda and k.is_cuda and v.is_cuda) or not (q.device == k.device == v.device):
+            raise ValueError("q, k, v must live on the same GPU (there is no CPU implementation of this operator)")
+    elif not (q.is_cuda and k.is_cuda and v.is_cuda and table.is_cuda) or not (q.device == k.device == v.device == table.device):
+        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
+
+
+def _check_fp8_cache(fn: str, q, kn: str, k, vn: str, v, table=None) -> None:
+    """dtype and device checks of the two fp8 entries: bf16 q, e4m3fn caches on q's GPU, the block table with them."""
+    for name, t in ((kn, k), (vn, v)):
+        if t.dtype == torch.uint8:
+            raise TypeError(f"{name} is torch.uint8: {fn} takes torch.float8_e4m3fn -- reinterpret the bytes with {name}.view(torch.float8_e4m3fn)")
+        if t.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"dtype {t.dtype} of {name} not supported by {fn} (torch.float8_e4m3fn)")
+    if q.dtype != torch.bfloat16:
+        raise TypeError(f"dtype {q.dtype} of q not supported by {fn} (bfloat16)")
+    if not (q.is_cuda and k.is_cuda and v.is_cuda) or not (q.device == k.device == v.device):
+        raise ValueError("q and the cache must live on the same GPU (there is no CPU implementation of this operator)")
+    if table is not None and (not table.is_cuda or table.device != q.device):
+        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
+
+
+class _Family(NamedTuple):
+    """what an element type of the cache changes in the front end"""
+    fp8: bool
+    contiguous: Tuple[str, str, str]   # the contiguous entry and its cache arguments, as messages name them
+    paged: Tuple[str, str, str]        # the paged entry and its pools
+    stride_multiple: int               # pool strides come in multiples of 16 bytes: this many elements
+    check_dtypes_and_devices: Callable
+
+
+_OUT_BF16 = {torch.bfloat16: _cabi.FA_DTYPE_BF16}   # out_dtype -> the C ABI's dtype code; everything else stores the fp32 accumulator
+_BF16 = _Family(False, ("forward_kv", "k", "v"), ("forward_paged", "k_pool", "v_pool"), 8, _check_bf16_cache)
+_FP8 = _Family(True, ("forward_kv_fp8", "k8", "v8"), ("forward_paged_fp8", "k_pool8", "v_pool8"), 16, _check_fp8_cache)
+
+# (fp8?, paged?, window?) -> the binding, its forward, its workspace query
+_ENTRIES = {
+    (False, False, False): (_cabi_kv, "fa_kv_forward", "fa_kv_workspace_bytes"),
+    (False, True, False): (_cabi_paged, "fa_paged_forward", "fa_paged_workspace_bytes"),
+    (True, False, False): (_cabi_kv8, "fa_kv8_forward", "fa_kv8_workspace_bytes"),
+    (True, True, False): (_cabi_kv8, "fa_kv8_paged_forward", "fa_kv8_workspace_bytes"),   # no paged query there: the contiguous one at batch * heads_kv
+    (False, False, True): (_cabi_kvw, "fa_kvw_forward", "fa_kvw_workspace_bytes"),
+    (False, True, True): (_cabi_kvw, "fa_kvw_paged_forward", "fa_kvw_paged_workspace_bytes"),
+    (True, False, True): (_cabi_kvw8, "fa_kvw8_forward", "fa_kvw8_workspace_bytes"),
+    (True, True, True): (_cabi_kvw8, "fa_kvw8_paged_forward", "fa_kvw8_paged_workspace_bytes"),
+}
+
+
+def _window(window_left: Optional[int]) -> Optional[int]:
+    """``window_left`` as the windowed entries take it: None (no window: the unwindowed libraries), or an int in 0 .. 2^24 (wider hides nothing)"""
+    if window_left is None:
+        return None
+    if isinstance(window_left, bool) or not isinstance(window_left, int):
+        raise TypeError(f"window_left must be None or an int, got {type(window_left).__name__}")
+    if window_left < 0:
+        raise ValueError(f"window_left = {window_left} must be >= 0 (None: no window)")
+    return min(window_left, 1 << 24)
+
+
+def _lens(name: str, lens: torch.Tensor, n: int, device) -> int:
+    """device pointer of ``kv_lens`` / ``seq_lens``: int32 ``(n,)`` on ``device``"""
+    if not isinstance(lens, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if lens.dtype != torch.int32 or lens.shape != (n,) or lens.device != device or not lens.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous torch.int32 tensor of shape ({n},) on {device}")
+    return lens.data_ptr()
+
+
+def _contiguous_cache(fam: _Family, q, k, v, kv_len, kv_lens):
+    """Validate q against a contiguous cache.  Returns q, k, v made contiguous, the shape as the queries take it (bh_kv, group, nq, nk, d)
+    and what a forward takes between ``lse`` and ``scale``."""
+    fn, kn, vn = fam.contiguous
+    for name, t in (("q", q), (kn, k), (vn, v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be 3-D (batch*heads, rows, head_dim), got shape {tuple(t.shape)}")
+    if k.shape != v.shape:
+        raise ValueError(f"{kn} and {vn} must have identical shapes, got {tuple(k.shape)}, {tuple(v.shape)}")
+    fam.check_dtypes_and_devices(fn, q, kn, k, vn, v)
+    bhq, nq, d = q.shape
+    bhkv, capacity, dk = k.shape
+    if dk != d:
+        raise ValueError(f"head_dim of q ({d}) and of {kn}, {vn} ({dk}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
+    if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
+        raise ValueError("empty batch or sequence")
+    if bhq % bhkv != 0:
+        raise ValueError(f"q has {bhq} slabs, {kn} / {vn} have {bhkv}: not a whole number of query heads per K/V head")
+    group = bhq // bhkv
+    nk = capacity if kv_len is None else int(kv_len)
+    if not 1 <= nk <= capacity:
+        raise ValueError(f"kv_len {nk} outside 1 .. capacity = {capacity}")
+    lens = None if kv_lens is None else _lens("kv_lens", kv_lens, bhkv, q.device)
+    return q.contiguous(), k.contiguous(), v.contiguous(), (bhkv, group, nq, nk, d), (bhkv, group, nq, nk, capacity, lens, d)
+
+
+def _paged_cache(fam: _Family, q, k_pool, v_pool, block_table, kv_len, seq_lens):
+    """Validate q against pools under a block table (a pool is never copied).  Returns q made contiguous, the ``fa_paged_cache`` and the
+    shape (batch, heads_kv, group, nq, nk, d): what the queries take, and a forward between ``lse`` and ``scale``."""
+    fn, kn, vn = fam.paged
+    for name, t in (("q", q), (kn, k_pool), (vn, v_pool), ("block_table", block_table)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if q.dim() != 3:
+        raise ValueError(f"q must be 3-D (batch*heads, rows, head_dim), got shape {tuple(q.shape)}")
+    if k_pool.dim() not in (3, 4):
+        raise ValueError(f"{kn} must be (pages, page, d) or (pages, page, H, d), got shape {tuple(k_pool.shape)}")
+    if k_pool.shape != v_pool.shape or k_pool.stride() != v_pool.stride():
+        raise ValueError(f"{kn} and {vn} must have identical shapes and strides, got {tuple(k_pool.shape)} / {k_pool.stride()} and "
+                         f"{tuple(v_pool.shape)} / {v_pool.stride()}")
+    fam.check_dtypes_and_devices(fn, q, kn, k_pool, vn, v_pool, block_table)
+    bhq, nq, d = q.shape
+    pages, page = k_pool.shape[0], k_pool.shape[1]
+    heads_kv = k_pool.shape[2] if k_pool.dim() == 4 else 1
+    if k_pool.shape[-1] != d:
+        raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool.shape[-1]}) differ")
+    if d not in KV_HEAD_DIMS:
+        raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
+    if k_pool.stride(-1) != 1:
+        raise ValueError(f"the pools' last stride must be 1, got {k_pool.stride(-1)} (a pool is never copied)")
+    page_stride, row_stride = k_pool.stride(0), k_pool.stride(1)
+    head_stride = k_pool.stride(2) if k_pool.dim() == 4 else 0
+    m = fam.stride_multiple
+    if page_stride % m or row_stride % m or head_stride % m:
+        raise ValueError(f"pool strides must be multiples of {m} elements (16 bytes), got {k_pool.stride()} (a pool is never copied)")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous():
+        raise ValueError("block_table must be a contiguous torch.int32 tensor of shape (batch, max_pages)")
+    batch, max_pages = block_table.shape
+    if bhq < 1 or nq < 1 or batch < 1 or max_pages < 1 or pages < 1 or heads_kv < 1:
+        raise ValueError("empty batch, sequence, pool or block table")
+    if bhq % (batch * heads_kv) != 0:
+        raise ValueError(f"q has {bhq} slabs, the cache {batch} sequences x {heads_kv} heads: not a whole number of query heads per K/V head")
+    group = bhq // (batch * heads_kv)
+    nk = max_pages * page if kv_len is None else int(kv_len)
+    if not 1 <= nk <= max_pages * page:
+        raise ValueError(f"kv_len {nk} outside 1 .. max_pages * page = {max_pages * page}")
+    cache = _cabi_paged.FaPagedCache(k_pool.data_ptr(), v_pool.data_ptr(), pages, page, page_stride, row_stride, head_stride,
+                                     block_table.data_ptr(), max_pages, None if seq_lens is None else _lens("seq_lens", seq_lens, batch, q.device))
+    return q.contiguous(), cache, (batch, heads_kv, group, nq, nk, d)
+
+
+def _workspace_need(fp8: bool, paged: bool, shape, causal: int, dt: int, window: tuple) -> int:
+    """``*_workspace_bytes`` of the library that runs (fp8?, paged?, window?) for ``shape`` as that query takes it; ``window``: () or (window_left,)"""
+    mod, _, query = _ENTRIES[fp8, paged, bool(window)]
+    if fp8 and paged and not window:
+        shape = (shape[0] * shape[1], *shape[2:])
+    return int(getattr(mod.lib(), query)(*shape, causal, dt, *window))
+
+
+def _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need):
+    """out, lse and workspace as the four entries prepare them"""
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
+    lse = torch.empty(q.shape[:2], dtype=torch.float32, device=q.device) if return_lse else None
+    return out, lse, _workspace(workspace, need, q.device)
+
+
+def _run(fam: _Family, paged: bool, window_left, q, cache, shape, dims, scale, scales, causal, return_lse, out, out_dtype, workspace):
+    """The call of (family, paged?, window?): ``cache`` is what a forward takes between ``q`` and ``o`` (two pointers, or the fa_paged_cache),
+    ``shape`` what the workspace query takes, ``dims`` what the forward takes between ``lse`` and ``scale``, ``scales`` the fp8 pair or ()."""
+    window = () if window_left is None else (window_left,)
+    causal = int(bool(causal))
+    mod, forward, _ = _ENTRIES[fam.fp8, paged, window_left is not None]
+    index = q.device.index   # device and stream by index: torch resolves a torch.device, or no device at all, through a slow path on every call
+    with torch.cuda.device(index):
+        dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
+        need = _workspace_need(fam.fp8, paged, shape, causal, dt, window)
+        out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
+        if scales:
+            scales = (float(scales[0]), float(scales[1]))
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = getattr(mod.lib(), forward)(q.data_ptr(), *cache, out.data_ptr(), lse.data_ptr() if lse is not None else None, *dims,
+                                         float(scale), *scales, causal, dt, *window,
+                                         workspace.data_ptr() if workspace is not None and workspace.numel() else None,
+                                         workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
+    mod.check(rc)
+    return (out, lse) if return_lse else out
 
 
 def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
@@ -159,90 +361,18 @@ def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     ``lo = max(0, len - nq - window_left)`` no K/V row below ``lo`` and none at or beyond ``len`` is ever read: rows that have slid out of
     the window may hold anything.  Pass the same ``window_left`` to ``workspace_bytes_kv``.
     """
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if t.dim() != 3:
-            raise ValueError(f"{name} must be 3-D (batch*heads, rows, head_dim), got shape {tuple(t.shape)}")
-    if k.shape != v.shape:
-        raise ValueError(f"k and v must have identical shapes, got {tuple(k.shape)}, {tuple(v.shape)}")
-    if not (q.dtype == k.dtype == v.dtype):
-        raise TypeError("q, k, v must share one dtype")
-    if q.dtype != torch.bfloat16:
-        raise TypeError(f"dtype {q.dtype} not supported by forward_kv (bfloat16: caches are 16-bit)")
-    if not (q.is_cuda and k.is_cuda and v.is_cuda) or not (q.device == k.device == v.device):
-        raise ValueError("q, k, v must live on the same GPU (there is no CPU implementation of this operator)")
-    bhq, nq, d = q.shape
-    bhkv, capacity, dk = k.shape
-    if dk != d:
-        raise ValueError(f"head_dim of q ({d}) and of k, v ({dk}) differ")
-    if d not in KV_HEAD_DIMS:
-        raise ValueError(f"head_dim {d} not supported by forward_kv (choose from {KV_HEAD_DIMS})")
-    if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
-        raise ValueError("empty batch or sequence")
-    if bhq % bhkv != 0:
-        raise ValueError(f"q has {bhq} slabs, k / v have {bhkv}: not a whole number of query heads per K/V head")
-    group = bhq // bhkv
-    nk = capacity if kv_len is None else int(kv_len)
-    if not 1 <= nk <= capacity:
-        raise ValueError(f"kv_len {nk} outside 1 .. capacity = {capacity}")
-    if kv_lens is not None:
-        if not isinstance(kv_lens, torch.Tensor):
-            raise TypeError("kv_lens must be a torch.Tensor")
-        if kv_lens.dtype != torch.int32 or kv_lens.shape != (bhkv,) or kv_lens.device != q.device or not kv_lens.is_contiguous():
-            raise ValueError(f"kv_lens must be a contiguous torch.int32 tensor of shape ({bhkv},) on {q.device}")
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    if out_dtype is None:
-        out_dtype = out.dtype if out is not None else q.dtype
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
-    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
-    if out is None:
-        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
-    lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
     window_left = _window(window_left)
-    L = _cabi_kv.lib() if window_left is None else _cabi_kvw.lib()
-    with torch.cuda.device(q.device):
-        if window_left is None:
-            need = int(L.fa_kv_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
-        else:
-            need = int(L.fa_kvw_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt, window_left))
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
-        elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
-            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
-        stream = torch.cuda.current_stream().cuda_stream
-        head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None, d, float(scale), int(bool(causal)), dt)
-        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-        rc = L.fa_kv_forward(*head, *tail) if window_left is None else L.fa_kvw_forward(*head, window_left, *tail)
-    (_cabi_kv if window_left is None else _cabi_kvw).check(rc)
-    return (out, lse) if return_lse else out
-
-
-def _window(window_left: Optional[int]) -> Optional[int]:
-    """``window_left`` as the windowed entries take it: None (no window: the unwindowed libraries), or an int in 0 .. 2^24 (wider hides nothing)"""
-    if window_left is None:
-        return None
-    if isinstance(window_left, bool) or not isinstance(window_left, int):
-        raise TypeError(f"window_left must be None or an int, got {type(window_left).__name__}")
-    if window_left < 0:
-        raise ValueError(f"window_left = {window_left} must be >= 0 (None: no window)")
-    return min(window_left, 1 << 24)
+    q, k, v, shape, dims = _contiguous_cache(_BF16, q, k, v, kv_len, kv_lens)
+    return _run(_BF16, False, window_left, q, (k.data_ptr(), v.data_ptr()), shape, dims, scale, (), causal, return_lse, out, out_dtype, workspace)
 
 
 def workspace_bytes_kv(bh_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *, out_dtype: torch.dtype = torch.bfloat16,
                        window_left: Optional[int] = None) -> int:
     """Bytes of scratch ``forward_kv`` can use for these shapes (``fa_kv_workspace_bytes``) and this ``window_left`` (``fa_kvw_workspace_bytes``:
     the plan is laid over ``min(nk, window_left + nq + 63)`` keys); 0 when the plan does not split the keys."""
-    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
     window_left = _window(window_left)
-    if window_left is not None:
-        return int(_cabi_kvw.lib().fa_kvw_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt, window_left))
-    return int(_cabi_kv.lib().fa_kv_workspace_bytes(int(bh_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
+    return _workspace_need(False, False, (int(bh_kv), int(group), int(nq), int(nk), int(d)), int(bool(causal)),
+                           _OUT_BF16.get(out_dtype, _cabi.FA_DTYPE_BF16_OUT_F32), () if window_left is None else (window_left,))
 
 
 def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
@@ -265,126 +395,18 @@ def forward_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, b
     ``len`` is read, and no table entry below ``lo // page`` or at or beyond ``ceil(len / page)``: pages that have slid out of the window can be
     freed or reused, and their entries may hold anything.  Pass the same ``window_left`` to ``workspace_bytes_paged``.
     """
-    for name, t in (("q", q), ("k_pool", k_pool), ("v_pool", v_pool), ("block_table", block_table)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if q.dim() != 3:
-        raise ValueError(f"q must be 3-D (batch*heads, rows, head_dim), got shape {tuple(q.shape)}")
-    if k_pool.dim() not in (3, 4):
-        raise ValueError(f"k_pool must be (pages, page, d) or (pages, page, H, d), got shape {tuple(k_pool.shape)}")
-    if k_pool.shape != v_pool.shape or k_pool.stride() != v_pool.stride():
-        raise ValueError(f"k_pool and v_pool must have identical shapes and strides, got {tuple(k_pool.shape)} / {k_pool.stride()} and "
-                         f"{tuple(v_pool.shape)} / {v_pool.stride()}")
-    if not (q.dtype == k_pool.dtype == v_pool.dtype):
-        raise TypeError("q, k_pool, v_pool must share one dtype")
-    if q.dtype != torch.bfloat16:
-        raise TypeError(f"dtype {q.dtype} not supported by forward_paged (bfloat16: caches are 16-bit)")
-    if not (q.is_cuda and k_pool.is_cuda and v_pool.is_cuda and block_table.is_cuda) or not (q.device == k_pool.device == v_pool.device == block_table.device):
-        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
-    bhq, nq, d = q.shape
-    pages, page = k_pool.shape[0], k_pool.shape[1]
-    heads_kv = k_pool.shape[2] if k_pool.dim() == 4 else 1
-    if k_pool.shape[-1] != d:
-        raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool.shape[-1]}) differ")
-    if d not in KV_HEAD_DIMS:
-        raise ValueError(f"head_dim {d} not supported by forward_paged (choose from {KV_HEAD_DIMS})")
-    if k_pool.stride(-1) != 1:
-        raise ValueError(f"the pools' last stride must be 1, got {k_pool.stride(-1)} (a pool is never copied)")
-    page_stride, row_stride = k_pool.stride(0), k_pool.stride(1)
-    head_stride = k_pool.stride(2) if k_pool.dim() == 4 else 0
-    if page_stride % 8 or row_stride % 8 or head_stride % 8:
-        raise ValueError(f"pool strides must be multiples of 8 elements (16 bytes), got {k_pool.stride()} (a pool is never copied)")
-    if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous():
-        raise ValueError("block_table must be a contiguous torch.int32 tensor of shape (batch, max_pages)")
-    batch, max_pages = block_table.shape
-    if bhq < 1 or nq < 1 or batch < 1 or max_pages < 1 or pages < 1 or heads_kv < 1:
-        raise ValueError("empty batch, sequence, pool or block table")
-    if bhq % (batch * heads_kv) != 0:
-        raise ValueError(f"q has {bhq} slabs, the cache {batch} sequences x {heads_kv} heads: not a whole number of query heads per K/V head")
-    group = bhq // (batch * heads_kv)
-    nk = max_pages * page if kv_len is None else int(kv_len)
-    if not 1 <= nk <= max_pages * page:
-        raise ValueError(f"kv_len {nk} outside 1 .. max_pages * page = {max_pages * page}")
-    if seq_lens is not None:
-        if not isinstance(seq_lens, torch.Tensor):
-            raise TypeError("seq_lens must be a torch.Tensor")
-        if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch,) or seq_lens.device != q.device or not seq_lens.is_contiguous():
-            raise ValueError(f"seq_lens must be a contiguous torch.int32 tensor of shape ({batch},) on {q.device}")
-    q = q.contiguous()
-    if out_dtype is None:
-        out_dtype = out.dtype if out is not None else q.dtype
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
-    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
-    if out is None:
-        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
-    lse = torch.empty((bhq, nq), dtype=torch.float32, device=q.device) if return_lse else None
-    cache = _cabi_paged.FaPagedCache(k_pool.data_ptr(), v_pool.data_ptr(), pages, page, page_stride, row_stride, head_stride,
-                                     block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
     window_left = _window(window_left)
-    L = _cabi_paged.lib() if window_left is None else _cabi_kvw.lib()
-    with torch.cuda.device(q.device):
-        if window_left is None:
-            need = int(L.fa_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt))
-        else:
-            need = int(L.fa_kvw_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt, window_left))
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
-        elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
-            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
-        stream = torch.cuda.current_stream().cuda_stream
-        head = (q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                batch, heads_kv, group, nq, nk, d, float(scale), int(bool(causal)), dt)
-        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-        rc = L.fa_paged_forward(*head, *tail) if window_left is None else L.fa_kvw_paged_forward(*head, window_left, *tail)
-    (_cabi_paged if window_left is None else _cabi_kvw).check(rc)
-    return (out, lse) if return_lse else out
+    q, cache, shape = _paged_cache(_BF16, q, k_pool, v_pool, block_table, kv_len, seq_lens)
+    return _run(_BF16, True, window_left, q, (ctypes.byref(cache),), shape, shape, scale, (), causal, return_lse, out, out_dtype, workspace)
 
 
 def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: int, d: int, causal: bool = False, *,
                           out_dtype: torch.dtype = torch.bfloat16, window_left: Optional[int] = None) -> int:
     """Bytes of scratch ``forward_paged`` can use for these shapes (``fa_paged_workspace_bytes`` = ``workspace_bytes_kv`` at ``batch * heads_kv``)
     and this ``window_left`` (``fa_kvw_paged_workspace_bytes``)."""
-    dt = _cabi.FA_DTYPE_BF16 if out_dtype == torch.bfloat16 else _cabi.FA_DTYPE_BF16_OUT_F32
     window_left = _window(window_left)
-    if window_left is not None:
-        return int(_cabi_kvw.lib().fa_kvw_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt,
-                                                                window_left))
-    return int(_cabi_paged.lib().fa_paged_workspace_bytes(int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d), int(bool(causal)), dt))
-
-
-def _check_fp8_cache(fn: str, q: torch.Tensor, named) -> None:
-    """dtype and device checks the two fp8 entries share: bf16 q, e4m3fn caches on q's GPU."""
-    for name, t in named:
-        if t.dtype == torch.uint8:
-            raise TypeError(f"{name} is torch.uint8: {fn} takes torch.float8_e4m3fn -- reinterpret the bytes with {name}.view(torch.float8_e4m3fn)")
-        if t.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"dtype {t.dtype} of {name} not supported by {fn} (torch.float8_e4m3fn)")
-    if q.dtype != torch.bfloat16:
-        raise TypeError(f"dtype {q.dtype} of q not supported by {fn} (bfloat16)")
-    if not q.is_cuda or any(not t.is_cuda or t.device != q.device for _, t in named):
-        raise ValueError("q and the cache must live on the same GPU (there is no CPU implementation of this operator)")
-
-
-def _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need):
-    """out, lse and workspace as forward_kv / forward_paged prepare them"""
-    if out_dtype is None:
-        out_dtype = out.dtype if out is not None else q.dtype
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError(f"out_dtype {out_dtype} not supported for {q.dtype} inputs")
-    if out is None:
-        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    elif out.shape != q.shape or out.dtype != out_dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError("out must be a contiguous tensor shaped like q with dtype out_dtype")
-    lse = torch.empty(q.shape[:2], dtype=torch.float32, device=q.device) if return_lse else None
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
-    elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous() or workspace.numel() < need:
-        raise ValueError(f"workspace must be a contiguous torch.uint8 tensor of at least {need} bytes on {q.device}")
-    return out, lse, workspace
+    return _workspace_need(False, True, (int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d)), int(bool(causal)),
+                           _OUT_BF16.get(out_dtype, _cabi.FA_DTYPE_BF16_OUT_F32), () if window_left is None else (window_left,))
 
 
 def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
@@ -407,52 +429,9 @@ def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
     result is bit for bit ``v_scale *`` that of ``forward_kv`` on the dequantised cache with the same ``window_left``.
     """
     window_left = _window(window_left)
-    for name, t in (("q", q), ("k8", k8), ("v8", v8)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if t.dim() != 3:
-            raise ValueError(f"{name} must be 3-D (batch*heads, rows, head_dim), got shape {tuple(t.shape)}")
-    if k8.shape != v8.shape:
-        raise ValueError(f"k8 and v8 must have identical shapes, got {tuple(k8.shape)}, {tuple(v8.shape)}")
-    _check_fp8_cache("forward_kv_fp8", q, (("k8", k8), ("v8", v8)))
-    bhq, nq, d = q.shape
-    bhkv, capacity, dk = k8.shape
-    if dk != d:
-        raise ValueError(f"head_dim of q ({d}) and of k8, v8 ({dk}) differ")
-    if d not in KV_HEAD_DIMS:
-        raise ValueError(f"head_dim {d} not supported by forward_kv_fp8 (choose from {KV_HEAD_DIMS})")
-    if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
-        raise ValueError("empty batch or sequence")
-    if bhq % bhkv != 0:
-        raise ValueError(f"q has {bhq} slabs, k8 / v8 have {bhkv}: not a whole number of query heads per K/V head")
-    group = bhq // bhkv
-    nk = capacity if kv_len is None else int(kv_len)
-    if not 1 <= nk <= capacity:
-        raise ValueError(f"kv_len {nk} outside 1 .. capacity = {capacity}")
-    if kv_lens is not None:
-        if not isinstance(kv_lens, torch.Tensor):
-            raise TypeError("kv_lens must be a torch.Tensor")
-        if kv_lens.dtype != torch.int32 or kv_lens.shape != (bhkv,) or kv_lens.device != q.device or not kv_lens.is_contiguous():
-            raise ValueError(f"kv_lens must be a contiguous torch.int32 tensor of shape ({bhkv},) on {q.device}")
-    q, k8, v8 = q.contiguous(), k8.contiguous(), v8.contiguous()
-    L = _cabi_kv8.lib() if window_left is None else _cabi_kvw8.lib()
-    with torch.cuda.device(q.device):
-        odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
-        dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
-        if window_left is None:
-            need = int(L.fa_kv8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt))
-        else:
-            need = int(L.fa_kvw8_workspace_bytes(bhkv, group, nq, nk, d, int(bool(causal)), dt, window_left))
-        out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
-        stream = torch.cuda.current_stream().cuda_stream
-        head = (q.data_ptr(), k8.data_ptr(), v8.data_ptr(), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                bhkv, group, nq, nk, capacity, kv_lens.data_ptr() if kv_lens is not None else None,
-                d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt)
-        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-        rc = L.fa_kv8_forward(*head, *tail) if window_left is None else L.fa_kvw8_forward(*head, window_left, *tail)
-    (_cabi_kv8 if window_left is None else _cabi_kvw8).check(rc)
-    return (out, lse) if return_lse else out
+    q, k8, v8, shape, dims = _contiguous_cache(_FP8, q, k8, v8, kv_len, kv_lens)
+    return _run(_FP8, False, window_left, q, (k8.data_ptr(), v8.data_ptr()), shape, dims, scale, (k_scale, v_scale), causal, return_lse, out, out_dtype,
+                workspace)
 
 
 def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
@@ -472,68 +451,8 @@ def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
     ``lo // page`` or at or beyond ``ceil(len / page)``: pages that have slid out can be freed or reused and may hold NaN codes.
     """
     window_left = _window(window_left)
-    for name, t in (("q", q), ("k_pool8", k_pool8), ("v_pool8", v_pool8), ("block_table", block_table)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if q.dim() != 3:
-        raise ValueError(f"q must be 3-D (batch*heads, rows, head_dim), got shape {tuple(q.shape)}")
-    if k_pool8.dim() not in (3, 4):
-        raise ValueError(f"k_pool8 must be (pages, page, d) or (pages, page, H, d), got shape {tuple(k_pool8.shape)}")
-    if k_pool8.shape != v_pool8.shape or k_pool8.stride() != v_pool8.stride():
-        raise ValueError(f"k_pool8 and v_pool8 must have identical shapes and strides, got {tuple(k_pool8.shape)} / {k_pool8.stride()} and "
-                         f"{tuple(v_pool8.shape)} / {v_pool8.stride()}")
-    _check_fp8_cache("forward_paged_fp8", q, (("k_pool8", k_pool8), ("v_pool8", v_pool8)))
-    if not block_table.is_cuda or block_table.device != q.device:
-        raise ValueError("q, the pools and the block table must live on the same GPU (there is no CPU implementation of this operator)")
-    bhq, nq, d = q.shape
-    pages, page = k_pool8.shape[0], k_pool8.shape[1]
-    heads_kv = k_pool8.shape[2] if k_pool8.dim() == 4 else 1
-    if k_pool8.shape[-1] != d:
-        raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool8.shape[-1]}) differ")
-    if d not in KV_HEAD_DIMS:
-        raise ValueError(f"head_dim {d} not supported by forward_paged_fp8 (choose from {KV_HEAD_DIMS})")
-    if k_pool8.stride(-1) != 1:
-        raise ValueError(f"the pools' last stride must be 1, got {k_pool8.stride(-1)} (a pool is never copied)")
-    page_stride, row_stride = k_pool8.stride(0), k_pool8.stride(1)
-    head_stride = k_pool8.stride(2) if k_pool8.dim() == 4 else 0
-    if page_stride % 16 or row_stride % 16 or head_stride % 16:
-        raise ValueError(f"pool strides must be multiples of 16 elements (16 bytes), got {k_pool8.stride()} (a pool is never copied)")
-    if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous():
-        raise ValueError("block_table must be a contiguous torch.int32 tensor of shape (batch, max_pages)")
-    batch, max_pages = block_table.shape
-    if bhq < 1 or nq < 1 or batch < 1 or max_pages < 1 or pages < 1 or heads_kv < 1:
-        raise ValueError("empty batch, sequence, pool or block table")
-    if bhq % (batch * heads_kv) != 0:
-        raise ValueError(f"q has {bhq} slabs, the cache {batch} sequences x {heads_kv} heads: not a whole number of query heads per K/V head")
-    group = bhq // (batch * heads_kv)
-    nk = max_pages * page if kv_len is None else int(kv_len)
-    if not 1 <= nk <= max_pages * page:
-        raise ValueError(f"kv_len {nk} outside 1 .. max_pages * page = {max_pages * page}")
-    if seq_lens is not None:
-        if not isinstance(seq_lens, torch.Tensor):
-            raise TypeError("seq_lens must be a torch.Tensor")
-        if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch,) or seq_lens.device != q.device or not seq_lens.is_contiguous():
-            raise ValueError(f"seq_lens must be a contiguous torch.int32 tensor of shape ({batch},) on {q.device}")
-    q = q.contiguous()
-    cache = _cabi_kv8.FaPagedCache(k_pool8.data_ptr(), v_pool8.data_ptr(), pages, page, page_stride, row_stride, head_stride,
-                                   block_table.data_ptr(), max_pages, seq_lens.data_ptr() if seq_lens is not None else None)
-    L = _cabi_kv8.lib() if window_left is None else _cabi_kvw8.lib()
-    with torch.cuda.device(q.device):
-        odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype)
-        dt = _cabi.FA_DTYPE_BF16_OUT_F32 if odt == torch.float32 else _cabi.FA_DTYPE_BF16
-        if window_left is None:
-            need = int(L.fa_kv8_workspace_bytes(batch * heads_kv, group, nq, nk, d, int(bool(causal)), dt))
-        else:
-            need = int(L.fa_kvw8_paged_workspace_bytes(batch, heads_kv, group, nq, nk, d, int(bool(causal)), dt, window_left))
-        out, lse, workspace = _out_lse_workspace(q, out, out_dtype, return_lse, workspace, need)
-        stream = torch.cuda.current_stream().cuda_stream
-        head = (q.data_ptr(), ctypes.byref(cache), out.data_ptr(), lse.data_ptr() if lse is not None else None,
-                batch, heads_kv, group, nq, nk, d, float(scale), float(k_scale), float(v_scale), int(bool(causal)), dt)
-        tail = (workspace.data_ptr() if workspace is not None and workspace.numel() else None,
-                workspace.numel() if workspace is not None else 0, ctypes.c_void_p(stream))
-        rc = L.fa_kv8_paged_forward(*head, *tail) if window_left is None else L.fa_kvw8_paged_forward(*head, window_left, *tail)
-    (_cabi_kv8 if window_left is None else _cabi_kvw8).check(rc)
-    return (out, lse) if return_lse else out
+    q, cache, shape = _paged_cache(_FP8, q, k_pool8, v_pool8, block_table, kv_len, seq_lens)
+    return _run(_FP8, True, window_left, q, (ctypes.byref(cache),), shape, shape, scale, (k_scale, v_scale), causal, return_lse, out, out_dtype, workspace)
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:

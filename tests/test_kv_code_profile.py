@@ -1,6 +1,8 @@
-"""CPU: the instruction profile of every kernel of the three KV-cache libraries (libflashattn_amd_kv.so, _paged.so, _kv8.so) against
-tests/golden/kv_kernel_profile.txt, recorded from a build of the commit before their decode loops, merges and validators were folded into
-shared headers (csrc/fa_kv_decode_core.h, fa_kv_combine_kernel.h, fa_kv_host.h).
+"""CPU: the instruction profile of every kernel of the five KV-cache libraries (libflashattn_amd_kv.so, _paged.so, _kv8.so, _kvw.so, _kvw8.so)
+against tests/golden/kv_kernel_profile.txt.  The lines of the first three were recorded from a build of the commit before their decode loops,
+merges and validators were folded into shared headers (csrc/fa_kv_decode_core.h, fa_kv_combine_kernel.h, fa_kv_host.h); the lines of the two
+windowed libraries (16 decode kernels + 2 merge kernels each) from a build of the commit before their build rules moved into one table, with the
+other 39 lines coming out unchanged.
 
 Sharing source text lets hipcc renumber scalar registers and move scalar / address instructions, so neither the bytes of a code object nor
 its instruction total are held.  What a change of these kernels must not move is held, per mangled kernel name:
@@ -18,12 +20,13 @@ import tempfile
 
 import pytest
 
-from flashattention_c_amd import _cabi_kv, _cabi_kv8, _cabi_paged
+from flashattention_c_amd import _cabi_kv, _cabi_kv8, _cabi_kvw, _cabi_kvw8, _cabi_paged
 from tests import codeobj
 from tests.conftest import GOLDEN_DIR
 
 GOLDEN = os.path.join(GOLDEN_DIR, "kv_kernel_profile.txt")
-LIBS = (("kv", _cabi_kv.LIB_PATH), ("paged", _cabi_paged.LIB_PATH), ("kv8", _cabi_kv8.LIB_PATH))
+LIBS = (("kv", _cabi_kv.LIB_PATH), ("paged", _cabi_paged.LIB_PATH), ("kv8", _cabi_kv8.LIB_PATH), ("kvw", _cabi_kvw.LIB_PATH),
+        ("kvw8", _cabi_kvw8.LIB_PATH))
 PREFIXES = ("v_mfma", "global_load", "ds_read", "ds_write", "global_store", "v_exp", "v_permlane", "v_cvt_pk", "s_barrier")
 
 
@@ -74,7 +77,7 @@ def test_every_kv_kernel_keeps_its_instruction_profile(tmp_path):
             want[f"{tag} {name}"] = rest
     have = current(str(tmp_path))
     assert set(have) == set(want), sorted(set(have) ^ set(want))
-    assert len(have) == 11 + 10 + 18
+    assert len(have) == 11 + 10 + 18 + 18 + 18   # kv, paged, kv8, kvw, kvw8
     bad = []
     for key in sorted(want):
         w, h = _fields(want[key]), _fields(have[key])
