@@ -1,4 +1,4 @@
-// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp, fa_kvw8_host.cpp): argument validation
+// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp, fa_kvw8_host.cpp, fa_kv256_host.cpp): argument validation
 // (no device is touched before it passes; lengths and block tables are device memory and never dereferenced here), the workspace and the
 // plan it selects, and the fill of the launch parameters.  Inline, like kv_plan: the libraries link no host object of each other.  The plan
 // is fa_kv.h's kv_plan over bh_kv = batch * heads_kv, so splits, share and workspace are the same in all of them for the same shapes (the windowed library: for the same span).
@@ -57,13 +57,23 @@ struct KvCall {
     size_t lse_bytes() const { return rows() * 4; }
 };
 
+// the head dims a library's kernels exist for: 64 and 128 in the five libraries over fa_kv_decode16_body.h / fa_kv8_decode_body.h, 256 alone in
+// the one over fa_kv256_decode_loop.h
+struct KvHeadDims {
+    int32_t a = 64, b = 128;
+};
+
 // the shape part of the validation, shared by every entry point and query
-inline int check_shape(KvError& e, const KvWords& w, int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t dtype)
+inline int check_shape(KvError& e, const KvWords& w, int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t dtype,
+                       KvHeadDims dims = {})
 {
     if (batch < 1 || heads_kv < 1 || group < 1 || nq < 1 || nk < 1) return e.fail(FA_ERR_INVALID_ARGUMENT, "%s, group, nq and nk must be >= 1", w.slabs);
     if (dtype == FA_DTYPE_F32) return e.fail(FA_ERR_UNSUPPORTED, "FA_DTYPE_F32 is not supported: %s (FA_DTYPE_BF16, FA_DTYPE_BF16_OUT_F32)", w.f32_why);
     if (dtype != FA_DTYPE_BF16 && dtype != FA_DTYPE_BF16_OUT_F32) return e.fail(FA_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-    if (d != 64 && d != 128) return e.fail(FA_ERR_UNSUPPORTED, "head dim %d is not supported: 64 or 128", d);
+    if (d != dims.a && d != dims.b) {
+        if (dims.a == dims.b) return e.fail(FA_ERR_UNSUPPORTED, "head dim %d is not supported: %d", d, dims.a);
+        return e.fail(FA_ERR_UNSUPPORTED, "head dim %d is not supported: %d or %d", d, dims.a, dims.b);
+    }
     if (nk > (1 << 24)) return e.fail(FA_ERR_UNSUPPORTED, "nk = %lld exceeds 2^24", (long long)nk);
     if (nq > (1 << 30) || (int64_t)group * nq > (1 << 30)) return e.fail(FA_ERR_UNSUPPORTED, "group * nq exceeds 2^30");
     if (batch > 0x7fffffffLL || batch * heads_kv > 0x7fffffffLL || batch * heads_kv * group > 0x7fffffffLL)
@@ -124,22 +134,22 @@ inline int check_capacity(KvError& e, const KvWords& w, int64_t nk, int32_t d, i
 
 // ---- a forward call in three steps, with the library's own checks of its scales between the first two ----
 // 1 (contiguous cache): pointers, shape, the slab's extent
-inline int check_cache(KvError& e, const KvWords& w, const KvCall& a, const void* k, const void* v, int64_t capacity)
+inline int check_cache(KvError& e, const KvWords& w, const KvCall& a, const void* k, const void* v, int64_t capacity, KvHeadDims dims = {})
 {
     if (a.q == nullptr || k == nullptr || v == nullptr || a.o == nullptr)
         return e.fail(FA_ERR_INVALID_ARGUMENT, "null pointer: q, %s, %s and o are required", w.k, w.v);
-    if (const int rc = check_shape(e, w, a.batch, a.heads_kv, a.group, a.nq, a.nk, a.d, a.dtype)) return rc;
+    if (const int rc = check_shape(e, w, a.batch, a.heads_kv, a.group, a.nq, a.nk, a.d, a.dtype, dims)) return rc;
     return check_capacity(e, w, a.nk, a.d, capacity);
 }
 
 // 1 (paged cache): pointers, shape, the geometry of the pool
-inline int check_pool(KvError& e, const KvWords& w, const KvCall& a, const fa_paged_cache* cache)
+inline int check_pool(KvError& e, const KvWords& w, const KvCall& a, const fa_paged_cache* cache, KvHeadDims dims = {})
 {
     if (a.q == nullptr || cache == nullptr || a.o == nullptr) return e.fail(FA_ERR_INVALID_ARGUMENT, "null pointer: q, cache and o are required");
     const fa_paged_cache& c = *cache;
     if (c.k_pool == nullptr || c.v_pool == nullptr || c.block_table == nullptr)
         return e.fail(FA_ERR_INVALID_ARGUMENT, "null pointer: k_pool, v_pool and block_table are required");
-    if (const int rc = check_shape(e, w, a.batch, a.heads_kv, a.group, a.nq, a.nk, a.d, a.dtype)) return rc;
+    if (const int rc = check_shape(e, w, a.batch, a.heads_kv, a.group, a.nq, a.nk, a.d, a.dtype, dims)) return rc;
     if (const int rc = check_page_size(e, c.page_size)) return rc;
     if (c.num_pages < 1 || c.num_pages > 0x7fffffffLL) return e.fail(FA_ERR_INVALID_ARGUMENT, "num_pages = %lld outside 1 .. 2^31 - 1", (long long)c.num_pages);
     if (c.max_pages < 1) return e.fail(FA_ERR_INVALID_ARGUMENT, "max_pages must be >= 1");

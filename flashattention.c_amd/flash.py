@@ -23,7 +23,7 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv256, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -143,6 +143,9 @@ def workspace_bytes(bh: int, n: int, d: int, causal: bool = False, *, dtype: tor
 
 
 KV_HEAD_DIMS = (64, 128)
+# ... of every KV-cache entry; the two 16-bit ones (forward_kv, forward_paged) take 256 as well (include/flashattn_amd_kv256.h).  The tuple and
+# the message built from it are pinned byte for byte by the recorded error texts, so the message undersells the 16-bit entries.
+KV_WIDE_HEAD_DIM = 256
 
 # ---- the four KV-cache entries: one front end.  What differs between a 16-bit and an fp8 cache is the _Family row, what differs between a contiguous
 # and a paged cache is the validator (_contiguous_cache / _paged_cache); library and symbols follow from (fp8?, paged?, window?) in _ENTRIES ----
@@ -202,6 +205,15 @@ _ENTRIES = {
 }
 
 
+def _entry(fp8: bool, paged: bool, d: int, window: tuple):
+    """binding, forward, workspace query and the window argument(s) of the library that runs (fp8?, paged?, window?) at head dim ``d``: a 16-bit
+    cache at d = 256 goes to the one library built for it, which takes ``window_left`` always (-1: no window)"""
+    if not fp8 and d == KV_WIDE_HEAD_DIM:
+        name = "fa_kv256_paged_" if paged else "fa_kv256_"
+        return _cabi_kv256, name + "forward", name + "workspace_bytes", window or (_cabi_kv256.NO_WINDOW,)
+    return (*_ENTRIES[fp8, paged, bool(window)], window)
+
+
 def _window(window_left: Optional[int]) -> Optional[int]:
     """``window_left`` as the windowed entries take it: None (no window: the unwindowed libraries), or an int in 0 .. 2^24 (wider hides nothing)"""
     if window_left is None:
@@ -238,7 +250,7 @@ def _contiguous_cache(fam: _Family, q, k, v, kv_len, kv_lens):
     bhkv, capacity, dk = k.shape
     if dk != d:
         raise ValueError(f"head_dim of q ({d}) and of {kn}, {vn} ({dk}) differ")
-    if d not in KV_HEAD_DIMS:
+    if d not in KV_HEAD_DIMS and (fam.fp8 or d != KV_WIDE_HEAD_DIM):
         raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
     if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
         raise ValueError("empty batch or sequence")
@@ -272,7 +284,7 @@ def _paged_cache(fam: _Family, q, k_pool, v_pool, block_table, kv_len, seq_lens)
     heads_kv = k_pool.shape[2] if k_pool.dim() == 4 else 1
     if k_pool.shape[-1] != d:
         raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool.shape[-1]}) differ")
-    if d not in KV_HEAD_DIMS:
+    if d not in KV_HEAD_DIMS and (fam.fp8 or d != KV_WIDE_HEAD_DIM):
         raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
     if k_pool.stride(-1) != 1:
         raise ValueError(f"the pools' last stride must be 1, got {k_pool.stride(-1)} (a pool is never copied)")
@@ -299,7 +311,7 @@ def _paged_cache(fam: _Family, q, k_pool, v_pool, block_table, kv_len, seq_lens)
 
 def _workspace_need(fp8: bool, paged: bool, shape, causal: int, dt: int, window: tuple) -> int:
     """``*_workspace_bytes`` of the library that runs (fp8?, paged?, window?) for ``shape`` as that query takes it; ``window``: () or (window_left,)"""
-    mod, _, query = _ENTRIES[fp8, paged, bool(window)]
+    mod, _, query, window = _entry(fp8, paged, shape[-1], window)
     if fp8 and paged and not window:
         shape = (shape[0] * shape[1], *shape[2:])
     return int(getattr(mod.lib(), query)(*shape, causal, dt, *window))
@@ -324,7 +336,7 @@ def _run(fam: _Family, paged: bool, window_left, q, cache, shape, dims, scale, s
     ``shape`` what the workspace query takes, ``dims`` what the forward takes between ``lse`` and ``scale``, ``scales`` the fp8 pair or ()."""
     window = () if window_left is None else (window_left,)
     causal = int(bool(causal))
-    mod, forward, _ = _ENTRIES[fam.fp8, paged, window_left is not None]
+    mod, forward, _, window = _entry(fam.fp8, paged, shape[-1], window)
     index = q.device.index   # device and stream by index: torch resolves a torch.device, or no device at all, through a slow path on every call
     with torch.cuda.device(index):
         dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
@@ -350,7 +362,7 @@ def forward_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     are attended to; ``BHq = BHkv * group``, query slab ``s`` reads K/V slab ``s // group``.  ``kv_lens``, an int32 tensor ``(BHkv,)`` on the
     device, gives each slab its own length (clamped to ``[0, kv_len]``); it is read by the kernel, never by the host, so a captured graph can
     be replayed while the cache grows.  ``causal`` is bottom-right aligned: query row ``i`` sees keys ``j <= len - nq + i``.  Rows without a
-    visible key get ``O = 0``, ``LSE = -inf``.  bfloat16 tensors, ``d`` 64 or 128; ``out_dtype=torch.float32`` stores the fp32 accumulator.
+    visible key get ``O = 0``, ``LSE = -inf``.  bfloat16 tensors, ``d`` 64, 128 or 256 (``include/flashattn_amd_kv256.h``); ``out_dtype=torch.float32`` stores the fp32 accumulator.
     Arithmetic and accuracy are those of ``forward(..., out_dtype=torch.float32)`` on bf16 tensors (P as two bf16 terms) for both outputs.
     Scratch (``workspace_bytes_kv``; key-split launches only) comes from ``torch.empty`` unless ``workspace`` passes a ``torch.uint8`` tensor.
 
