@@ -8,7 +8,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
 
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
-The six KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
+The seven KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
 sources) are always built beside it.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
@@ -64,7 +64,8 @@ ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
 # the turn of the library it belongs to, and its OBJECT is linked into each.  No library exports a symbol of another: what else they share (plan,
 # decode loop, validator) is inline in csrc/fa_kv*.h.
 EXT_LIBS = {
-    "kv256": ["fa_kv256_decode.hip", "fa_kv_combine.hip", "fa_kv256_host.cpp"],  # head dim 256 over a bf16 cache: a decode loop of its own (32-key blocks)
+    "kv8_256": ["fa_kv8_256_decode.hip", "fa_kv8_combine.hip", "fa_kv8_256_host.cpp"],  # head dim 256 over an fp8 cache: the 32-key block with the fp8 data movement
+    "kv256":["fa_kv256_decode.hip", "fa_kv_combine.hip", "fa_kv256_host.cpp"],  # head dim 256 over a bf16 cache: a decode loop of its own (32-key blocks)
     "kv8": ["fa_kv8_decode.hip", "fa_kv8_combine.hip", "fa_kv8_host.cpp"],      # contiguous and paged over an fp8 (e4m3fn) cache: one decode kernel template
     "kvw8": ["fa_kvw8_decode.hip", "fa_kv8_combine.hip", "fa_kvw8_host.cpp"],   # the fp8 decode loop under a sliding window (WINDOW = true)
     "kvw": ["fa_kvw_decode.hip", "fa_kv_combine.hip", "fa_kvw_host.cpp"],       # the 16-bit decode loop under a sliding window, contiguous and paged
@@ -91,6 +92,7 @@ EXTRA_FLAGS = {f"fa_split_{dt}_d{d}.hip": ["-fno-slp-vectorize"] for dt in ("f32
 EXTRA_FLAGS["experiments/fa_fwd_f32_t3.hip"] = ["-fno-slp-vectorize"]
 # the d = 256 decode loop rescales 144 accumulator registers per block: kept as scalar v_mul_f32 (no v_pk_mul_f32 beside the matrix pipe)
 EXTRA_FLAGS["fa_kv256_decode.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS["fa_kv8_256_decode.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]   # the same rescale, the same reasoning
 
 
 def hipcc() -> str:
@@ -144,7 +146,7 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        # one pool for all seven libraries: the extension libraries' sources first (each distinct one once), then the product's
+        # one pool for all eight libraries: the extension libraries' sources first (each distinct one once), then the product's
         ext_futs = {s: ex.submit(_compile, s, force) for tag, srcs in EXT_LIBS.items() for s in srcs if SHARED_OBJECTS.get(s, tag) == tag}
         objs = list(ex.map(lambda s: _compile(s, force), LIB_SOURCES))
         ext_objs = {tag: [ext_futs[s].result() for s in srcs] for tag, srcs in EXT_LIBS.items()}

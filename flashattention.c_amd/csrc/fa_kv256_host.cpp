@@ -11,17 +11,6 @@ static const KvWords kKv256Words = {2, "bh_kv", "caches are 16-bit", "bh_kv * gr
 static const KvWords kKv256PagedWords = {2, "batch, heads_kv", "caches are 16-bit", "batch * heads_kv * group", "fa_kv256_paged_workspace_bytes", "k", "v", "q, k, v, o"};
 static constexpr KvHeadDims kKv256Dims = {kKv256HeadDim, kKv256HeadDim};
 
-// -1: no window (*w = -1); >= 0: check_window's saturation at 2^24
-static int check_window_or_none(KvError& e, int32_t window_left, int32_t* w)
-{
-    if (window_left < -1) return e.fail(FA_ERR_INVALID_ARGUMENT, "window_left = %d must be >= 0, or -1 for no window", window_left);
-    *w = -1;
-    return window_left < 0 ? FA_OK : check_window(e, window_left, w);
-}
-
-// the keys the plan is laid over (plan_call: 0 stands for nk)
-static int64_t span_of(int64_t nq, int64_t nk, int32_t w) { return w < 0 ? 0 : kvw_span(nq, nk, w); }
-
 // shape and window of a query (no pointers): the plan of the call, or nothing
 static bool plan_query(const KvWords& words, int64_t batch, int32_t heads_kv, int32_t group, int64_t nq, int64_t nk, int32_t d, int32_t dtype,
                        int32_t window_left, KvPlan* pl)
@@ -75,7 +64,7 @@ int fa_kv256_forward(const void* q, const void* k, const void* v, void* o, float
     if (const int rc = check_scale(e, scale)) return rc;
     Kv256Params wp{};
     if (const int rc = check_window_or_none(e, window_left, &wp.window_left)) return rc;
-    if (const int rc = plan_cache(e, kKv256Words, a, k, v, capacity, kv_lens, scale, wp.pp.kv, span_of(nq, nk, wp.window_left))) return rc;
+    if (const int rc = plan_cache(e, kKv256Words, a, k, v, capacity, kv_lens, scale, wp.pp.kv, span_or_none(nq, nk, wp.window_left))) return rc;
     hipError_t err = launch_kv256_decode(wp, 0, wp.window_left >= 0, causal != 0, a.out_f32(), (hipStream_t)stream);
     if (err == hipSuccess && wp.pp.kv.splits > 1) err = launch_kv_combine(wp.pp.kv, d, a.out_f32(), (hipStream_t)stream);
     return launch_result(e, err);
@@ -110,7 +99,7 @@ int fa_kv256_paged_forward(const void* q, const fa_paged_cache* cache, void* o, 
     if (const int rc = check_scale(e, scale)) return rc;
     Kv256Params wp{};
     if (const int rc = check_window_or_none(e, window_left, &wp.window_left)) return rc;
-    if (const int rc = plan_pool(e, kKv256PagedWords, a, *cache, scale, wp.pp, span_of(nq, nk, wp.window_left))) return rc;
+    if (const int rc = plan_pool(e, kKv256PagedWords, a, *cache, scale, wp.pp, span_or_none(nq, nk, wp.window_left))) return rc;
     hipError_t err = launch_kv256_decode(wp, 1, wp.window_left >= 0, causal != 0, a.out_f32(), (hipStream_t)stream);
     if (err == hipSuccess && wp.pp.kv.splits > 1) err = launch_kv_combine(wp.pp.kv, d, a.out_f32(), (hipStream_t)stream);
     return launch_result(e, err);

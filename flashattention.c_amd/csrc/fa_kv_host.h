@@ -1,4 +1,4 @@
-// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp, fa_kvw8_host.cpp, fa_kv256_host.cpp): argument validation
+// fa_kv_host.h -- the host side the KV-cache libraries share (fa_kv_plan.cpp, fa_paged_host.cpp, fa_kv8_host.cpp, fa_kvw_host.cpp, fa_kvw8_host.cpp, fa_kv256_host.cpp, fa_kv8_256_host.cpp): argument validation
 // (no device is touched before it passes; lengths and block tables are device memory and never dereferenced here), the workspace and the
 // plan it selects, and the fill of the launch parameters.  Inline, like kv_plan: the libraries link no host object of each other.  The plan
 // is fa_kv.h's kv_plan over bh_kv = batch * heads_kv, so splits, share and workspace are the same in all of them for the same shapes (the windowed library: for the same span).
@@ -58,7 +58,7 @@ struct KvCall {
 };
 
 // the head dims a library's kernels exist for: 64 and 128 in the five libraries over fa_kv_decode16_body.h / fa_kv8_decode_body.h, 256 alone in
-// the one over fa_kv256_decode_loop.h
+// the two over fa_kv256_decode_loop.h and fa_kv8_256_decode_loop.h
 struct KvHeadDims {
     int32_t a = 64, b = 128;
 };
@@ -116,6 +116,17 @@ inline int check_window(KvError& e, int32_t window_left, int32_t* w)
     *w = window_left < kKvwMaxWindow ? window_left : kKvwMaxWindow;
     return FA_OK;
 }
+
+// ... where -1 stands for "no window" (the two libraries at d = 256, fa_kv256.h and fa_kv8_256.h): *w = -1 then, check_window's saturation otherwise
+inline int check_window_or_none(KvError& e, int32_t window_left, int32_t* w)
+{
+    if (window_left < -1) return e.fail(FA_ERR_INVALID_ARGUMENT, "window_left = %d must be >= 0, or -1 for no window", window_left);
+    *w = -1;
+    return window_left < 0 ? FA_OK : check_window(e, window_left, w);
+}
+
+// the keys the plan of such a call is laid over (plan_call: 0 stands for nk)
+inline int64_t span_or_none(int64_t nq, int64_t nk, int32_t w) { return w < 0 ? 0 : kvw_span(nq, nk, w); }
 
 inline bool overlaps(const void* a, size_t na, const void* b, size_t nb)
 {

@@ -23,7 +23,7 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv256, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -143,8 +143,8 @@ def workspace_bytes(bh: int, n: int, d: int, causal: bool = False, *, dtype: tor
 
 
 KV_HEAD_DIMS = (64, 128)
-# ... of every KV-cache entry; the two 16-bit ones (forward_kv, forward_paged) take 256 as well (include/flashattn_amd_kv256.h).  The tuple and
-# the message built from it are pinned byte for byte by the recorded error texts, so the message undersells the 16-bit entries.
+# ... of every KV-cache entry; all four take 256 as well (include/flashattn_amd_kv256.h, include/flashattn_amd_kv8_256.h).  The tuple and
+# the message built from it are pinned byte for byte by the recorded error texts, so the message undersells the entries.
 KV_WIDE_HEAD_DIM = 256
 
 # ---- the four KV-cache entries: one front end.  What differs between a 16-bit and an fp8 cache is the _Family row, what differs between a contiguous
@@ -207,10 +207,11 @@ _ENTRIES = {
 
 def _entry(fp8: bool, paged: bool, d: int, window: tuple):
     """binding, forward, workspace query and the window argument(s) of the library that runs (fp8?, paged?, window?) at head dim ``d``: a 16-bit
-    cache at d = 256 goes to the one library built for it, which takes ``window_left`` always (-1: no window)"""
-    if not fp8 and d == KV_WIDE_HEAD_DIM:
-        name = "fa_kv256_paged_" if paged else "fa_kv256_"
-        return _cabi_kv256, name + "forward", name + "workspace_bytes", window or (_cabi_kv256.NO_WINDOW,)
+    cache at d = 256 goes to the one library built for it, which takes ``window_left`` always (-1: no window), and so does an fp8 cache"""
+    if d == KV_WIDE_HEAD_DIM:
+        mod, name = (_cabi_kv8_256, "fa_kv8_256_") if fp8 else (_cabi_kv256, "fa_kv256_")
+        name += "paged_" if paged else ""
+        return mod, name + "forward", name + "workspace_bytes", window or (mod.NO_WINDOW,)
     return (*_ENTRIES[fp8, paged, bool(window)], window)
 
 
@@ -250,7 +251,7 @@ def _contiguous_cache(fam: _Family, q, k, v, kv_len, kv_lens):
     bhkv, capacity, dk = k.shape
     if dk != d:
         raise ValueError(f"head_dim of q ({d}) and of {kn}, {vn} ({dk}) differ")
-    if d not in KV_HEAD_DIMS and (fam.fp8 or d != KV_WIDE_HEAD_DIM):
+    if d not in KV_HEAD_DIMS and d != KV_WIDE_HEAD_DIM:
         raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
     if bhq < 1 or nq < 1 or bhkv < 1 or capacity < 1:
         raise ValueError("empty batch or sequence")
@@ -284,7 +285,7 @@ def _paged_cache(fam: _Family, q, k_pool, v_pool, block_table, kv_len, seq_lens)
     heads_kv = k_pool.shape[2] if k_pool.dim() == 4 else 1
     if k_pool.shape[-1] != d:
         raise ValueError(f"head_dim of q ({d}) and of the pools ({k_pool.shape[-1]}) differ")
-    if d not in KV_HEAD_DIMS and (fam.fp8 or d != KV_WIDE_HEAD_DIM):
+    if d not in KV_HEAD_DIMS and d != KV_WIDE_HEAD_DIM:
         raise ValueError(f"head_dim {d} not supported by {fn} (choose from {KV_HEAD_DIMS})")
     if k_pool.stride(-1) != 1:
         raise ValueError(f"the pools' last stride must be 1, got {k_pool.stride(-1)} (a pool is never copied)")
@@ -432,8 +433,8 @@ def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
     tensor and call.  The kernel dequantises to bf16 exactly and runs the arithmetic of ``forward_kv``; ``k_scale`` is folded into ``scale`` as
     one fp32 product, ``v_scale`` multiplies the normalised result once, the LSE is that of the scaled scores.  With ``v_scale`` a power of two
     the result is bit for bit ``v_scale * forward_kv(q, k8.to(bfloat16), v8.to(bfloat16), scale=fp32(scale * k_scale))``.  Everything else --
-    ``kv_len``, ``kv_lens``, ``causal``, rows without keys, ``d``, output dtypes -- is ``forward_kv``'s; scratch has the size ``workspace_bytes_kv``
-    gives for the same shapes and ``window_left``.
+    ``kv_len``, ``kv_lens``, ``causal``, rows without keys, ``d`` (64, 128 or 256: ``include/flashattn_amd_kv8_256.h``), output dtypes -- is
+    ``forward_kv``'s; scratch has the size ``workspace_bytes_kv`` gives for the same shapes and ``window_left``.
 
     ``window_left`` (``include/flashattn_amd_kvw8.h``; ``None``: no window) is ``forward_kv``'s sliding window with its rules: an ``int >= 0``
     (negative raises ``ValueError``), only the keys of the window are walked, and with ``lo = max(0, len - nq - window_left)`` no cache byte of a
@@ -450,7 +451,8 @@ def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
                       k_scale: float = 1.0, v_scale: float = 1.0, seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None,
                       scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                       workspace: Optional[torch.Tensor] = None, window_left: Optional[int] = None):
-    """``forward_paged`` over pools of 8-bit floats (``include/flashattn_amd_kv8.h``); scales and arithmetic as in ``forward_kv_fp8``.
+    """``forward_paged`` over pools of 8-bit floats (``include/flashattn_amd_kv8.h``; ``d`` = 256: ``include/flashattn_amd_kv8_256.h``); scales and
+    arithmetic as in ``forward_kv_fp8``.
 
     ``k_pool8``, ``v_pool8`` are ``torch.float8_e4m3fn`` ``(pages, page, d)`` or ``(pages, page, H, d)`` (``torch.uint8`` is rejected: ``.view`` it).
     Their strides are taken as they are and a pool is never copied: a last stride other than 1 or a stride that is not a multiple of 16

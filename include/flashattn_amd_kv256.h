@@ -39,7 +39,7 @@
  *             on the shapes and on window_left only, never on lengths.  NULL or 0 bytes: the call runs unsplit.  Non-NULL but
  *             too small: FA_ERR_INVALID_ARGUMENT.  Contents need no initialisation.
  *
- * Out of scope: fp8 caches at d = 256, head dims 96, 160 and 192.
+ * fp8 caches at d = 256: include/flashattn_amd_kv8_256.h.  Out of scope: head dims 96, 160 and 192.
  */
 #ifndef FLASHATTN_AMD_KV256_H
 #define FLASHATTN_AMD_KV256_H
