@@ -8,7 +8,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
 
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
-The seven KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
+The eight KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
 sources) are always built beside it.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
@@ -64,6 +64,7 @@ ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
 # the turn of the library it belongs to, and its OBJECT is linked into each.  No library exports a symbol of another: what else they share (plan,
 # decode loop, validator) is inline in csrc/fa_kv*.h.
 EXT_LIBS = {
+    "kvp": ["fa_kvp_prefill.hip", "fa_kvp_host.cpp"],                           # chunked prefill over the bf16 caches at d = 128: 256-row tiles, K/V through LDS, no merge kernel
     "kv8_256": ["fa_kv8_256_decode.hip", "fa_kv8_combine.hip", "fa_kv8_256_host.cpp"],  # head dim 256 over an fp8 cache: the 32-key block with the fp8 data movement
     "kv256":["fa_kv256_decode.hip", "fa_kv_combine.hip", "fa_kv256_host.cpp"],  # head dim 256 over a bf16 cache: a decode loop of its own (32-key blocks)
     "kv8": ["fa_kv8_decode.hip", "fa_kv8_combine.hip", "fa_kv8_host.cpp"],      # contiguous and paged over an fp8 (e4m3fn) cache: one decode kernel template
@@ -93,6 +94,7 @@ EXTRA_FLAGS["experiments/fa_fwd_f32_t3.hip"] = ["-fno-slp-vectorize"]
 # the d = 256 decode loop rescales 144 accumulator registers per block: kept as scalar v_mul_f32 (no v_pk_mul_f32 beside the matrix pipe)
 EXTRA_FLAGS["fa_kv256_decode.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS["fa_kv8_256_decode.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]   # the same rescale, the same reasoning
+EXTRA_FLAGS["fa_kvp_prefill.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]      # ... of 160 registers, and the softmax of 64 rows per wave beside the matrix pipe
 
 
 def hipcc() -> str:

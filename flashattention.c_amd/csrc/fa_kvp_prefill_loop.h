@@ -1,0 +1,332 @@
+// fa_kvp_prefill_loop.h -- chunked prefill over a bf16 cache at head dim 128, contiguous or paged: the kernel of libflashattn_amd_kvp.so
+// (fa_kvp_prefill.hip instantiates it eight times).  The compute-bound twin of the decode loop (fa_kv_decode16_body.h): the same packed rows,
+// the same masks, the same arithmetic, the opposite split of the work.  No counterpart in the reference.
+// Out of scope: fp8 caches, window_left, d = 64 / 256, a key split for tiny grids, routing from fa_kv_forward.
+//
+// Work split.  A workgroup of four waves owns (K/V slab, 256-row tile of the slab's packed rows); wave w takes rows 64 w .. 64 w + 63 of the
+// tile as two 32-row blocks (nb = 0, 1).  All four waves walk the SAME 64-key blocks, from key 0 to the tile's kend = min(len, diag + imax + 1):
+// no key split, no workspace, no merge.  Causal tiles are launched heaviest first.
+//
+// K and V through LDS, shared by the waves.  Each 64-key block is brought in once per workgroup by LDS-DMA (global_load_lds, 16 bytes per
+// lane), a quarter of the 1 KiB pieces per wave: K into the row-major, slot-swizzled 16 KiB image of fa_bf16_common.h, V into its
+// [key/4][col/16][4][16] image.  Two stages of (K, V): 64 KiB, one barrier per block --
+//     wait for my pieces of block j;  barrier;  enqueue block j + 1 into the other stage;  compute block j
+// -- the barrier says both "block j has landed in full" and "everybody is done reading block j - 1", whose stage block j + 1 overwrites.
+// The DMA of block j + 1 has all of block j's arithmetic to land in, so the wait at the top (vmcnt(0): nothing else is outstanding) is free.
+// The LDS reads are inline asm, counted by hand: hipcc puts "wait for EVERY LDS-DMA in flight" in front of each LDS read it can see.
+// A wave reads each K fragment (ds_read_b128) and each V^T fragment (ds_read_b64_tr_b16) once and feeds it to both of its row blocks: two
+// matrix instructions per LDS read, 256 rows of matrix work per K/V byte fetched (the decode kernel: 32).
+//
+// Registers (one wave per SIMD, 512; the code object: 256 + 236, no scratch).  O (2 x 64) and the row sums (2 x 16) live in the accumulation
+// half, and hipcc puts the scores there as well.  Q is 64 registers and fits neither half beside the rest when a whole 64-key block's scores
+// and P (64 + 64) are live, so a block is computed as two halves of 32 keys -- the 32-key softmax step of fa_kv256_decode_loop.h -- with 32 + 32
+// live, the K fragments of a half (32) and two sets of V^T fragments (2 x 16) beside them; Q's first row block is pinned in the vector half, its
+// second in the accumulation half (only the matrix pipe reads it).  The price is a second maximum / rescale test per block.
+//
+// Arithmetic: the contract of the KV libraries.  S^T = K Q^T on v_mfma_f32_32x32x16_bf16, one bf16 product; the mask, the maximum and the
+// -inf-safe m_use of kv_mask_and_max; P = bf16 hi + bf16 lo (kv_p_terms); the row sum on the matrix pipe against all-ones in the sequence of
+// every O column.  The softmax step is per 32 keys (above).  The accumulators are rescaled only in a step where some row's maximum moved (a wave-uniform branch; alpha = 1 elsewhere,
+// so the bits are those of the unconditional product): they live in the accumulation half, which the vector ALU reaches through moves only.
+//
+// Edges: rows past M are computed on zeros and never stored; i = r % nq, so tiles and blocks may straddle heads; loads of rows at or beyond
+// kend are redirected to row kend - 1 BEFORE the table lookup (fetch_pages clamps the same way); a tile without a visible key never touches
+// K, V or the table and stores 0 / -inf.  A wave whose rows see nothing of a block (above its diagonal, or all past M) skips the block's matrix
+// work, but still brings its pieces in and meets the barrier.
+// Paged: the address rule of fa_kv_decode_core.h.  Piece i of a wave (i = 0 .. 3) holds rows 16 i + 4 wave .. + 3 of the block, so its page
+// is entry i of the block's four: a compile-time index.  The entries are read through the constant address space one block ahead of the DMA
+// that uses them.  A 64-bit uniform base plus a 32-bit offset per lane, under the host checks of fa_kv_host.h.
+#pragma once
+#include "fa_kv256_decode_loop.h"
+#include "fa_kvp.h"
+
+namespace fa {
+
+struct KvpCfg {
+    static constexpr int D = kKvpHeadDim, KS = D / 16, DB = D / 32, NB = 2;
+    static constexpr int kImage = kKvBlk * 2 * D;                 // bytes of one K or V image (64 keys)
+    static constexpr int kStage = 2 * kImage;                     // K, then V
+    static constexpr int kPieces = kImage / 1024 / kKvWaves;      // 1 KiB DMA pieces per wave and image
+    static_assert(kKvpRowTile == kKvWaves * NB * kKvRowTile, "four waves of two row blocks");
+    static_assert(kPieces == kPagedBlockPages && 1024 / (2 * D) * kKvWaves == kPagedMinPage, "piece i of a wave lies in the block's 16-row group i");
+    static_assert(2 * kStage <= 64 * 1024, "two stages");
+};
+
+__device__ __forceinline__ bf16x8 lds_read_b128(unsigned addr)
+{
+    bf16x8 v;
+    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+    return v;
+}
+// all but the N most recent LDS reads have landed (they return in order; a table entry in flight on the same counter only makes the wait
+// stricter), and nothing the compiler schedules may use x[] before this point
+template <int N, typename T, int K>
+__device__ __forceinline__ void lds_landed_but(T (&x)[K])
+{
+    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+#pragma unroll
+    for (int i = 0; i < K; ++i) asm volatile("" : "+v"(x[i]));
+}
+
+template <bool CAUSAL, bool OUT_F32, bool PAGED>
+__device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
+{
+    using C = KvpCfg;
+    constexpr int D = C::D, KS = C::KS, DB = C::DB, NB = C::NB, NP = kPagedBlockPages;
+    __shared__ __attribute__((aligned(1024))) char smem[2 * C::kStage];
+
+    const PagedParams& pp = wp.pp;
+    const KvParams& p = pp.kv;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lq = lane & 31, hi = lane >> 5;
+    const int M = p.m_rows, nq = p.nq;
+
+    // ---- the workgroup's tile: slab fastest (the XCDs take workgroups round robin: a slab's tiles meet in one L2 where bh_kv is a multiple
+    // of 8), tiles in the order u = 0, 1, ... with the heaviest causal tile first ----
+    const int slab = blockIdx.x % p.bh_kv, u = blockIdx.x / p.bh_kv;
+    int tile = u;
+    if (CAUSAL) {
+        tile = wp.tiles - 1 - u;
+        if (nq % kKvpRowTile == 0) {   // tiles do not straddle heads: the last tile of every head, then the one before it, ...
+            const int per_head = nq / kKvpRowTile, group = M / nq;
+            tile = (u % group) * per_head + per_head - 1 - u / group;
+        }
+    }
+    int heads_kv = 1;
+    if constexpr (PAGED) heads_kv = pp.heads_kv;
+    const int seq = slab / heads_kv, head = slab % heads_kv;
+    int len = p.nk;
+    if (p.kv_lens != nullptr) len = min(max(p.kv_lens[seq], 0), p.nk);
+    const int diag = len - nq;
+    // the keys a range of packed rows reads: [0, end), bounded by the range's widest row (0: no row of the slab in it)
+    auto keys_of = [&](int r0, int rows) {
+        if (r0 >= M) return 0;
+        const int rl = min(r0 + rows - 1, M - 1);
+        int end = len;
+        if (CAUSAL) end = min(end, diag + ((r0 / nq != rl / nq) ? nq - 1 : rl % nq) + 1);
+        return max(end, 0);
+    };
+    const int row0 = tile * kKvpRowTile, wrow0 = row0 + wave * (NB * kKvRowTile);
+    const int kend = keys_of(row0, kKvpRowTile);
+    const int wend = __builtin_amdgcn_readfirstlane(keys_of(wrow0, NB * kKvRowTile));   // this wave's rows see nothing at or beyond it
+    const int nblk = (kend + kKvBlk - 1) / kKvBlk;
+
+    // ---- Q, the masks ----
+    bf16x8 qf[NB][KS];
+    int lim[NB];
+    bool row_ok[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        const int r0 = wrow0 + nb * kKvRowTile;
+        row_ok[nb] = r0 + lq < M;
+        lim[nb] = kend - 1;
+        if (CAUSAL) lim[nb] = min(lim[nb], diag + (r0 + lq) % nq);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[nb][ks] = kv_q_fragment<D>(p.q, (int64_t)slab * M + min(r0, M - 1), row_ok[nb], lq, hi, ks);
+    }
+    auto q_in_registers = [&]() {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (nb == 0) asm volatile("" : "+v"(qf[nb][ks]));
+                else asm volatile("" : "+a"(qf[nb][ks]));
+            }
+    };
+    q_in_registers();
+    bf16x8 ones;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
+
+    const __bf16 *kg, *vg;
+    cst_i32_t* tbl = nullptr;
+    int page_mask = 0;
+    unsigned row_stride = 0;
+    if constexpr (PAGED) {
+        kg = (const __bf16*)p.k + (int64_t)head * pp.head_stride;
+        vg = (const __bf16*)p.v + (int64_t)head * pp.head_stride;
+        tbl = (cst_i32_t*)(pp.table + (int64_t)seq * pp.max_pages);
+        page_mask = (1 << pp.page_shift) - 1;
+        row_stride = (unsigned)pp.row_stride;
+    } else {
+        kg = (const __bf16*)p.k + (int64_t)slab * p.kv_slab_stride;
+        vg = (const __bf16*)p.v + (int64_t)slab * p.kv_slab_stride;
+    }
+
+    // ---- this lane's part of a piece: its row within the piece's 16-row group and its column (issue_k_tile / issue_v_tile of
+    // fa_bf16_common.h for piece wave + 4 i: the swizzle of a K row depends on the row's low four bits, which i does not touch) ----
+    const int k_row = 4 * wave + (lane >> 4), k_col = ((lane & 15) ^ (k_row & 15)) * 8;
+    const int v_row = 4 * wave + ((lane & 7) >> 1), v_col = (lane >> 3) * 16 + (lane & 1) * 8;
+    auto issue = [&](int kv0, const int64_t(&pb)[NP], char* stage) {
+#pragma unroll
+        for (int i = 0; i < C::kPieces; ++i) {
+            const int kr = min(kv0 + 16 * i + k_row, kend - 1), vr = min(kv0 + 16 * i + v_row, kend - 1);
+            const char *ks, *vs;
+            if constexpr (PAGED) {
+                ks = (const char*)(kg + pb[i]) + ((unsigned)(kr & page_mask) * row_stride + k_col) * 2u;
+                vs = (const char*)(vg + pb[i]) + ((unsigned)(vr & page_mask) * row_stride + v_col) * 2u;
+            } else {
+                ks = (const char*)kg + ((unsigned)kr * (unsigned)(2 * D) + k_col * 2);
+                vs = (const char*)vg + ((unsigned)vr * (unsigned)(2 * D) + v_col * 2);
+            }
+            __builtin_amdgcn_global_load_lds((gbl_cvoid_t*)ks, (lds_void_t*)(stage + (wave + kKvWaves * i) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_cvoid_t*)vs, (lds_void_t*)(stage + C::kImage + (wave + kKvWaves * i) * 1024), 16, 0, 0);
+        }
+    };
+
+    // ---- this lane's corners of the fragments ----
+    // K: key kb * 32 + lq of the image, columns 16 ks + 8 hi .. + 8 = slot 2 ks + hi, swizzled by the row's low four bits
+    const unsigned k_lane_off = lq * (2 * D), k_g = lq & 15;
+    // V^T: [key/4][col/16][4][16] sub-tiles, keys permuted like the scores (fa_kv_decode16_body.h)
+    const int li = lane & 15;
+    const unsigned v_lane_off = C::kImage + (hi * (D / 16) + ((lane >> 4) & 1)) * 128 + (li >> 2) * 32 + (li & 3) * 8;
+    const float c = p.scale_log2e;
+
+    f32x16 o[NB][DB], lacc[NB];
+    float m[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        m[nb] = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lacc[nb][r] = 0.0f;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[nb][db][r] = 0.0f;
+    }
+
+    // the V^T fragments of 16 keys (kb, t) for all four column blocks of O
+    auto read_v = [&](unsigned v_addr, int f, s16x4(&vv)[2 * DB]) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+            vv[2 * db] = lds_read_tr16(v_addr + (((f >> 1) * 8 + 4 * (f & 1) + 0) * (D / 16) + 2 * db) * 128);
+            vv[2 * db + 1] = lds_read_tr16(v_addr + (((f >> 1) * 8 + 4 * (f & 1) + 2) * (D / 16) + 2 * db) * 128);
+        }
+    };
+
+    // One 64-key block, as two halves of 32 keys (one MFMA row block of S^T each, with the 32-key softmax step of fa_kv256_decode_loop.h): the
+    // scores and P of both row blocks are 32 + 32 registers live at a time instead of 64 + 64, which is what lets Q stay in registers.
+    auto compute = [&](int kv0, unsigned stage) __attribute__((always_inline)) {
+        const unsigned k_addr = stage + k_lane_off, v_addr = stage + v_lane_off;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (h == 1 && kv0 + 32 >= wend) break;   // the wave's rows see nothing of the second half
+            // ---- S^T = K Q^T ----
+            bf16x8 kf[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) kf[ks] = lds_read_b128(k_addr + h * 32 * (2 * D) + (((2 * ks + hi) ^ k_g) * 16));
+            f32x16 s[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[nb][r] = 0.0f;
+            lds_landed_but<0>(kf);
+            s16x4 va[2 * DB], vb[2 * DB];
+            read_v(v_addr, 2 * h, va);   // lands under the products and the softmax
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) s[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[nb][ks], s[nb], 0, 0, 0);
+
+            // ---- online softmax, per row block ----
+            bf16x8 ph[NB][2], pl[NB][2];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const KvRescale rs = kv256_mask_and_max<false>(s[nb], lim[nb] - kv0 - 32 * h - 4 * hi, c, m[nb], 0);
+                if (__builtin_amdgcn_ballot_w64(rs.alpha != 1.0f) != 0) {   // some row's maximum moved
+#pragma unroll
+                    for (int db = 0; db < DB; ++db)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) o[nb][db][r] *= rs.alpha;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) lacc[nb][r] *= rs.alpha;
+                }
+                kv256_p_terms(s[nb], rs.m_use, ph[nb], pl[nb]);
+            }
+
+            // ---- O^T += V^T P^T, 16 keys at a time: the second 16 keys' fragments in flight under the first's products ----
+            auto pv = [&](int t, const s16x4(&vv)[2 * DB]) {
+#pragma unroll
+                for (int db = 0; db < DB; ++db) {
+                    const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(vv[2 * db], vv[2 * db + 1], 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        o[nb][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph[nb][t], o[nb][db], 0, 0, 0);
+                        o[nb][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pl[nb][t], o[nb][db], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    lacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, ph[nb][t], lacc[nb], 0, 0, 0);
+                    lacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pl[nb][t], lacc[nb], 0, 0, 0);
+                }
+            };
+            read_v(v_addr, 2 * h + 1, vb);
+            lds_landed_but<2 * DB>(va);
+            pv(0, va);
+            lds_landed_but<0>(vb);
+            pv(1, vb);
+            q_in_registers();
+        }
+    };
+
+    // ---- the walk ----
+    int64_t pg[NP];
+    int ent[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) pg[i] = 0, ent[i] = 0;
+    if (nblk > 0) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
+        if constexpr (PAGED) {
+            int e0[NP];
+            fetch_pages(tbl, pp.page_shift, 0, kend, e0);
+            fetch_pages(tbl, pp.page_shift, kKvBlk, kend, ent);
+            pages_landed(e0, pp.page_stride, pg);
+        }
+        issue(0, pg, smem);
+    }
+    const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
+    for (int j = 0; j < nblk; ++j) {
+        wait_lds_dma();                  // my pieces of block j
+        __builtin_amdgcn_s_barrier();    // everybody's; and everybody has read block j - 1
+        asm volatile("" ::: "memory");
+        const int par = j & 1;
+        if (j + 1 < nblk) {
+            if constexpr (PAGED) {
+                pages_landed(ent, pp.page_stride, pg);                              // block j + 1: fetched a block ago
+                fetch_pages(tbl, pp.page_shift, (j + 2) * kKvBlk, kend, ent);       // block j + 2
+            }
+            issue((j + 1) * kKvBlk, pg, smem + (par ^ 1) * C::kStage);
+        }
+        if (j * kKvBlk < wend) compute(j * kKvBlk, lds0 + par * C::kStage);
+    }
+    mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight
+
+    // ---- epilogue: every wave stores its own rows.  Lane (lq, hi) holds columns 32 db + 8 g + 4 hi .. + 4 of row lq in o[.][db][4 g ..] ----
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        if (!row_ok[nb]) continue;
+        const float l = lacc[nb][0];
+        const bool none = !(l > 0.0f);   // no visible key: O = 0, LSE = -inf
+        const int64_t prow = (int64_t)slab * M + wrow0 + nb * kKvRowTile + lq;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 acc;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = none ? 0.0f : o[nb][db][4 * g + e] / l;
+                const int col = db * 32 + 8 * g + 4 * hi;
+                if (OUT_F32) {
+                    *(f32x4*)((float*)p.o + prow * D + col) = acc;
+                } else {
+                    bf16x4 r;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) r[e] = (__bf16)acc[e];
+                    *(bf16x4*)((__bf16*)p.o + prow * D + col) = r;
+                }
+            }
+        if (hi == 0 && p.lse != nullptr) p.lse[prow] = none ? -INFINITY : (m[nb] + __builtin_amdgcn_logf(l)) * kLn2;
+    }
+}
+
+}  // namespace fa

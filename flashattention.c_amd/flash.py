@@ -23,9 +23,9 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
-__all__ = ["forward", "forward_kv", "forward_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
+__all__ = ["forward", "forward_kv", "forward_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
            "SUPPORTED_HEAD_DIMS", "KV_HEAD_DIMS"]
 
@@ -420,6 +420,52 @@ def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: in
     window_left = _window(window_left)
     return _workspace_need(False, True, (int(batch), int(heads_kv), int(group), int(nq), int(nk), int(d)), int(bool(causal)),
                            _OUT_BF16.get(out_dtype, _cabi.FA_DTYPE_BF16_OUT_F32), () if window_left is None else (window_left,))
+
+
+PREFILL_HEAD_DIM = 128   # the one head dim of the chunked-prefill kernels (include/flashattn_amd_kvp.h)
+
+
+def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_lse, out, out_dtype):
+    """The call of a chunked-prefill entry: ``_run`` without a window, scales or a workspace (the kernel has no key split)."""
+    if q.shape[-1] != PREFILL_HEAD_DIM:
+        raise ValueError(f"head_dim {q.shape[-1]} not supported by {fn} ({PREFILL_HEAD_DIM}; forward_{fn[8:]} takes {KV_HEAD_DIMS} and {KV_WIDE_HEAD_DIM})")
+    index = q.device.index
+    with torch.cuda.device(index):
+        dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
+        out, lse, _ = _out_lse_workspace(q, out, out_dtype, return_lse, None, 0)
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = getattr(_cabi_kvp.lib(), forward)(q.data_ptr(), *cache, out.data_ptr(), lse.data_ptr() if lse is not None else None, *dims,
+                                               float(scale), int(bool(causal)), dt, ctypes.c_void_p(stream))
+    _cabi_kvp.check(rc)
+    return (out, lse) if return_lse else out
+
+
+def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
+               kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None,
+               out_dtype: Optional[torch.dtype] = None):
+    """``forward_kv`` for MANY query rows (``include/flashattn_amd_kvp.h``): chunked prefill against a K/V cache, ``d = 128``, bfloat16.
+
+    Arguments, masking (``causal`` bottom-right aligned), ``kv_len`` / ``kv_lens`` (read on the device only), rows without a visible key,
+    output dtypes, arithmetic and accuracy are ``forward_kv``'s; the results agree with it to that accuracy, not bit for bit.  The kernel is the
+    other one: a workgroup owns 256 packed rows (``group * nq`` rows share a K/V slab) and every 64-key block passes through LDS once for all
+    of them, where ``forward_kv`` streams the whole slab once per 32 rows.  No key split, so no workspace -- and a call whose
+    ``BHkv * ceil(group * nq / 256)`` workgroups are fewer than the 256 CUs leaves CUs idle.  Which to call (``docs/kv_prefill.md``, measured
+    at ``BHkv = 8``, ``nk = 8192``): ``prefill_kv`` is 1.2 - 1.3x faster at ``group * nq = 8192`` (one workgroup per CU) and 1.4x SLOWER at
+    ``group * nq = 4096`` (half the CUs); the crossover is near ``group * nq = 6000`` there, i.e. ``BHkv * group * nq`` of about 48 000 packed
+    rows.  Below it call ``forward_kv``.  No ``window_left``, no fp8 caches, no other head dim.
+    """
+    q, k, v, _, dims = _contiguous_cache(_BF16, q, k, v, kv_len, kv_lens)
+    return _run_prefill("prefill_kv", "fa_kvp_forward", q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype)
+
+
+def prefill_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
+                  seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None, scale: float = 1.0, return_lse: bool = False,
+                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+    """``prefill_kv`` over a paged cache: ``forward_paged``'s arguments and rules (pools never copied, pages of 16 .. 65536 rows, table and
+    ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read) on the chunked-prefill kernel, ``d = 128``.  The
+    result is ``prefill_kv``'s on the gathered cache, bit for bit."""
+    q, cache, shape = _paged_cache(_BF16, q, k_pool, v_pool, block_table, kv_len, seq_lens)
+    return _run_prefill("prefill_paged", "fa_kvp_paged_forward", q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype)
 
 
 def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
