@@ -6,8 +6,8 @@ Import name: ``flashattention_c_amd`` (the directory name contains a dot; ``flas
 aliases it).
 """
 from . import _cabi, _cabi_ext, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvw, _cabi_kvw8, _cabi_paged  # noqa: F401
-from .flash import KV_HEAD_DIMS, SUPPORTED_HEAD_DIMS, forward, forward_kv, forward_paged, prefill_kv, prefill_paged, forward_kv_fp8, forward_paged_fp8, forward_packed_qkv, workspace_bytes_kv, workspace_bytes_paged, last_forward_route, load, stats, time_forward, workspace_bytes  # noqa: F401
+from .flash import KV_HEAD_DIMS, SUPPORTED_HEAD_DIMS, forward, forward_kv, forward_paged, prefill_kv, prefill_paged, forward_kv_fp8, forward_paged_fp8, prefill_kv_fp8, prefill_paged_fp8, forward_packed_qkv, workspace_bytes_kv, workspace_bytes_paged, last_forward_route, load, stats, time_forward, workspace_bytes  # noqa: F401
 from .sharding import forward_sharded, shard_range, shard_sizes  # noqa: F401
 
-__all__ = ["forward", "forward_kv", "workspace_bytes_kv", "forward_paged", "workspace_bytes_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "KV_HEAD_DIMS", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "forward_sharded", "shard_range", "shard_sizes", "workspace_bytes",
+__all__ = ["forward", "forward_kv", "workspace_bytes_kv", "forward_paged", "workspace_bytes_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "prefill_kv_fp8", "prefill_paged_fp8", "KV_HEAD_DIMS", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "forward_sharded", "shard_range", "shard_sizes", "workspace_bytes",
            "stats", "SUPPORTED_HEAD_DIMS"]

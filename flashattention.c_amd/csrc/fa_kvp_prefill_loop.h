@@ -1,7 +1,8 @@
 // fa_kvp_prefill_loop.h -- chunked prefill over a bf16 cache at head dim 128, contiguous or paged: the kernel of libflashattn_amd_kvp.so
 // (fa_kvp_prefill.hip instantiates it eight times).  The compute-bound twin of the decode loop (fa_kv_decode16_body.h): the same packed rows,
 // the same masks, the same arithmetic, the opposite split of the work.  No counterpart in the reference.
-// Out of scope: fp8 caches, window_left, d = 64 / 256, a key split for tiny grids, routing from fa_kv_forward.
+// With FP8 = true it is the kernel of libflashattn_amd_kvp8.so over a cache of e4m3 bytes (fa_kvp8_prefill.hip; "FP8" below and Kvp8Map).
+// Out of scope: window_left, d = 64 / 256, a key split for tiny grids, routing from fa_kv_forward.
 //
 // Work split.  A workgroup of four waves owns (K/V slab, 256-row tile of the slab's packed rows); wave w takes rows 64 w .. 64 w + 63 of the
 // tile as two 32-row blocks (nb = 0, 1).  All four waves walk the SAME 64-key blocks, from key 0 to the tile's kend = min(len, diag + imax + 1):
@@ -35,9 +36,26 @@
 // Paged: the address rule of fa_kv_decode_core.h.  Piece i of a wave (i = 0 .. 3) holds rows 16 i + 4 wave .. + 3 of the block, so its page
 // is entry i of the block's four: a compile-time index.  The entries are read through the constant address space one block ahead of the DMA
 // that uses them.  A 64-bit uniform base plus a 32-bit offset per lane, under the host checks of fa_kv_host.h.
+//
+// FP8 (one text: everything above is compiled as it is, `if constexpr (FP8)` replaces how a block gets into a stage; with FP8 = false the
+// code objects are what they were).  An e4m3 byte cannot ride the LDS-DMA: it has to pass the converter.  So
+//     my stores of block j have landed (lgkmcnt(0));  barrier;  load the raw bytes of block j + 1 (four 16-byte loads per lane: 16 registers
+//     held across the compute -- the code object: 256 + 253 where the bf16 kernel has 256 + 236, no scratch);  compute block j;  convert (cvt_fp8x8, exact) and store block j + 1 into the
+//     other stage as eight ds_write_b128
+// with block 0 loaded, converted and stored in front of the loop.  The one barrier keeps both meanings: the stage written at the end of block
+// j was last read in block j - 1, which every wave left before the barrier at the top of block j.  The images are the bf16 kernel's byte for
+// byte (Kvp8Map says how the lanes are laid over a block so that neither image's stores meet in a bank), so the hand-counted reads, the
+// softmax halves, the matrix instructions and the epilogue are the same instructions on the same bits; v_scale multiplies once behind the
+// quotient.  Against the hand-counted lgkmcnt waits of the compute: the stores are issued behind the block's last wait (lds_landed_but<0>(vb))
+// and drained by the lgkmcnt(0) in front of the barrier, so none is outstanding while lds_landed_but counts reads; the paged scalar loads sit
+// where the bf16 kernel has them, between the barrier and the compute, and an entry in flight only makes a counted wait stricter (above).  A
+// wave's two loads of a block lie in one 16-row group each (2 i + wave / 2), so it fetches two entries per block, not four.
 #pragma once
 #include "fa_kv256_decode_loop.h"
+#include "fa_kv8_decode_core.h"
 #include "fa_kvp.h"
+
+#include <type_traits>
 
 namespace fa {
 
@@ -50,6 +68,45 @@ struct KvpCfg {
     static_assert(kPieces == kPagedBlockPages && 1024 / (2 * D) * kKvWaves == kPagedMinPage, "piece i of a wave lies in the block's 16-row group i");
     static_assert(2 * kStage <= 64 * 1024, "two stages");
 };
+
+// FP8 (fa_kvp8_prefill.hip): how a 64-key block of e4m3 bytes is split over the workgroup.  A row is 128 bytes = eight 16-byte chunks of 16
+// columns; a wave-load is eight whole rows (1 KiB), and load i of wave w is rows 32 i + 8 w .. + 7 of the block for K and for V alike: inside
+// ONE 16-row group, 2 i + w / 2, so the wave needs two table entries per block and both are wave-uniform.
+//   K  lane l: row (l >> 3) of the eight, chunk l & 7.  The 32 bytes of bf16 are slots 2 c and 2 c + 1 of the row, kept at (2 c) ^ g and
+//      (2 c) ^ g ^ 1, g = row & 15.  The eight lanes of a row write eight different slots of one 256-byte row, and the row beside them (g ^ 1)
+//      the other eight: no two lanes of a ds_write_b128 pass meet in a bank.
+//   V  lane l: key 4 (l >> 5) + ((l >> 1) & 3) of the eight, chunk (l & 1) + 2 ((l >> 3) & 3).  A chunk is one 32-byte row of one 128-byte
+//      sub-tile, at (key / 4) * 1024 + chunk * 128 + (key % 4) * 32.  With chunk = l & 7 the eight lanes of a pass would hold ONE key and eight
+//      sub-tiles 128 bytes apart: the same 32 bytes of every 256, four lanes to a bank (what v8x256_swz is for at d = 256).  Here the eight
+//      consecutive lanes hold (chunk & 1, key % 4) in all eight combinations, i.e. eight different 32-byte rows of a 256-byte span, so the image
+//      stays the bf16 kernel's byte for byte and its reads stay as they are: the permutation is in the loads, where it costs nothing (a
+//      wave-load still covers eight whole rows).
+struct Kvp8Map {
+    static constexpr int kLoads = 2;                             // 16-byte loads per lane, block and tensor
+    static constexpr int kRowsPerLoad = 8 * kKvWaves;            // rows of the block between a wave's two loads
+    static constexpr int kLoadImage = kRowsPerLoad * 2 * KvpCfg::D;   // ... and their bytes in a bf16 image
+    static_assert(kLoads * kRowsPerLoad == kKvBlk && 8 <= kPagedMinPage && kPagedMinPage % 8 == 0, "eight rows of a load lie in one 16-row group");
+    static_assert(KvpCfg::D == 128, "a row is eight 16-byte chunks of e4m3");
+};
+
+// fetch_pages / pages_landed of fa_kv_decode_core.h for the two loads of a wave: rows row0 and row0 + kRowsPerLoad of the block, clamped to
+// kend - 1 BEFORE the lookup (only called with kend >= 1)
+__device__ __forceinline__ void kvp8_fetch_pages(cst_i32_t* tbl, int page_shift, int row0, int kend, int (&e)[Kvp8Map::kLoads])
+{
+#pragma unroll
+    for (int i = 0; i < Kvp8Map::kLoads; ++i) {
+        int idx = __builtin_amdgcn_readfirstlane(min(row0 + i * Kvp8Map::kRowsPerLoad, kend - 1)) >> page_shift;
+        asm volatile("" : "+s"(idx));
+        e[i] = tbl[idx];
+    }
+}
+__device__ __forceinline__ void kvp8_pages_landed(int (&e)[Kvp8Map::kLoads], int64_t page_stride, int64_t (&pb)[Kvp8Map::kLoads])
+{
+#pragma unroll
+    for (int i = 0; i < Kvp8Map::kLoads; ++i) asm volatile("" : "+s"(e[i]));
+#pragma unroll
+    for (int i = 0; i < Kvp8Map::kLoads; ++i) pb[i] = (int64_t)e[i] * page_stride;
+}
 
 __device__ __forceinline__ bf16x8 lds_read_b128(unsigned addr)
 {
@@ -67,11 +124,12 @@ __device__ __forceinline__ void lds_landed_but(T (&x)[K])
     for (int i = 0; i < K; ++i) asm volatile("" : "+v"(x[i]));
 }
 
-template <bool CAUSAL, bool OUT_F32, bool PAGED>
-__device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
+template <bool CAUSAL, bool OUT_F32, bool PAGED, bool FP8 = false, typename Params = KvpParams>
+__device__ __forceinline__ void kvp_prefill(const Params& wp)
 {
     using C = KvpCfg;
-    constexpr int D = C::D, KS = C::KS, DB = C::DB, NB = C::NB, NP = kPagedBlockPages;
+    using elem_t = std::conditional_t<FP8, uint8_t, __bf16>;   // FP8: one byte per element, so every offset of the cache is in bytes
+    constexpr int D = C::D, KS = C::KS, DB = C::DB, NB = C::NB, NP = FP8 ? Kvp8Map::kLoads : kPagedBlockPages;
     __shared__ __attribute__((aligned(1024))) char smem[2 * C::kStage];
 
     const PagedParams& pp = wp.pp;
@@ -138,19 +196,19 @@ __device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
 #pragma unroll
     for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
 
-    const __bf16 *kg, *vg;
+    const elem_t *kg, *vg;
     cst_i32_t* tbl = nullptr;
     int page_mask = 0;
     unsigned row_stride = 0;
     if constexpr (PAGED) {
-        kg = (const __bf16*)p.k + (int64_t)head * pp.head_stride;
-        vg = (const __bf16*)p.v + (int64_t)head * pp.head_stride;
+        kg = (const elem_t*)p.k + (int64_t)head * pp.head_stride;
+        vg = (const elem_t*)p.v + (int64_t)head * pp.head_stride;
         tbl = (cst_i32_t*)(pp.table + (int64_t)seq * pp.max_pages);
         page_mask = (1 << pp.page_shift) - 1;
         row_stride = (unsigned)pp.row_stride;
     } else {
-        kg = (const __bf16*)p.k + (int64_t)slab * p.kv_slab_stride;
-        vg = (const __bf16*)p.v + (int64_t)slab * p.kv_slab_stride;
+        kg = (const elem_t*)p.k + (int64_t)slab * p.kv_slab_stride;
+        vg = (const elem_t*)p.v + (int64_t)slab * p.kv_slab_stride;
     }
 
     // ---- this lane's part of a piece: its row within the piece's 16-row group and its column (issue_k_tile / issue_v_tile of
@@ -158,6 +216,7 @@ __device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
     const int k_row = 4 * wave + (lane >> 4), k_col = ((lane & 15) ^ (k_row & 15)) * 8;
     const int v_row = 4 * wave + ((lane & 7) >> 1), v_col = (lane >> 3) * 16 + (lane & 1) * 8;
     auto issue = [&](int kv0, const int64_t(&pb)[NP], char* stage) {
+        if constexpr (!FP8)
 #pragma unroll
         for (int i = 0; i < C::kPieces; ++i) {
             const int kr = min(kv0 + 16 * i + k_row, kend - 1), vr = min(kv0 + 16 * i + v_row, kend - 1);
@@ -173,6 +232,51 @@ __device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
             __builtin_amdgcn_global_load_lds((gbl_cvoid_t*)vs, (lds_void_t*)(stage + C::kImage + (wave + kKvWaves * i) * 1024), 16, 0, 0);
         }
     };
+
+    // ---- FP8: the block through registers (Kvp8Map).  raw[i] is K's load i, raw[kLoads + i] V's: ordinary loads, counted in vmcnt by hipcc.
+    // The lane's coordinates are derived from its number where they are used, behind an empty statement, not held through the loop ----
+    constexpr int NL = Kvp8Map::kLoads;
+    int lane_v = lane;
+    auto load_raw = [&](int kv0, const int64_t(&pb)[NP], u32x4(&raw)[2 * NL]) {
+        if constexpr (FP8) {
+            asm volatile("" : "+v"(lane_v));
+            const int k_key = 8 * wave + (lane_v >> 3), k_chunk = lane_v & 7;
+            const int v_key = 8 * wave + 4 * (lane_v >> 5) + ((lane_v >> 1) & 3), v_chunk = (lane_v & 1) + 2 * ((lane_v >> 3) & 3);
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                const int kr = min(kv0 + i * Kvp8Map::kRowsPerLoad + k_key, kend - 1), vr = min(kv0 + i * Kvp8Map::kRowsPerLoad + v_key, kend - 1);
+                const uint8_t *ks, *vs;
+                if constexpr (PAGED) {
+                    ks = kg + pb[i] + ((unsigned)(kr & page_mask) * row_stride + k_chunk * 16);
+                    vs = vg + pb[i] + ((unsigned)(vr & page_mask) * row_stride + v_chunk * 16);
+                } else {
+                    ks = kg + ((unsigned)kr * (unsigned)D + k_chunk * 16);
+                    vs = vg + ((unsigned)vr * (unsigned)D + v_chunk * 16);
+                }
+                raw[i] = *(const u32x4*)ks;
+                raw[NL + i] = *(const u32x4*)vs;
+            }
+            asm volatile("" ::: "memory");   // the loads stay in front of the block's compute: they are what is in flight under it
+        }
+    };
+    // ... converted exactly and written into the two bf16 images of `stage` (an LDS byte offset), two ds_write_b128 per load
+    auto convert_store = [&](const u32x4(&raw)[2 * NL], int stage) {
+        if constexpr (FP8) {
+            asm volatile("" : "+v"(lane_v));
+            const int k_key = 8 * wave + (lane_v >> 3), v_key4 = 2 * wave + (lane_v >> 5), v_chunk = (lane_v & 1) + 2 * ((lane_v >> 3) & 3);
+            const int k_wr = stage + k_key * (2 * D) + (((2 * (lane_v & 7)) ^ (k_key & 15)) << 4);
+            const int v_wr = stage + C::kImage + v_key4 * 1024 + v_chunk * 128 + ((lane_v >> 1) & 3) * 32;
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                *(bf16x8*)(smem + i * Kvp8Map::kLoadImage + k_wr) = cvt_fp8x8(raw[i][0], raw[i][1]);
+                *(bf16x8*)(smem + i * Kvp8Map::kLoadImage + (k_wr ^ 16)) = cvt_fp8x8(raw[i][2], raw[i][3]);
+                *(bf16x8*)(smem + i * Kvp8Map::kLoadImage + v_wr) = cvt_fp8x8(raw[NL + i][0], raw[NL + i][1]);
+                *(bf16x8*)(smem + i * Kvp8Map::kLoadImage + v_wr + 16) = cvt_fp8x8(raw[NL + i][2], raw[NL + i][3]);
+            }
+        }
+    };
+    // my stores have landed (and, PAGED, the entries in flight: they are a block old)
+    auto stores_landed = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
 
     // ---- this lane's corners of the fragments ----
     // K: key kb * 32 + lq of the image, columns 16 ks + 8 hi .. + 8 = slot 2 ks + hi, swizzled by the row's low four bits
@@ -275,29 +379,48 @@ __device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
     int ent[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) pg[i] = 0, ent[i] = 0;
+    // the entries of the block at kv0 (FP8: of this wave's two loads of it), and the point up to which they must have arrived
+    auto fetch = [&](int kv0, int(&e)[NP]) {
+        if constexpr (FP8) kvp8_fetch_pages(tbl, pp.page_shift, kv0 + 8 * wave, kend, e);
+        else fetch_pages(tbl, pp.page_shift, kv0, kend, e);
+    };
+    auto landed = [&](int(&e)[NP]) {
+        if constexpr (FP8) kvp8_pages_landed(e, pp.page_stride, pg);
+        else pages_landed(e, pp.page_stride, pg);
+    };
+    u32x4 raw[2 * NL];   // FP8: the bytes of the next block, from the top of a block to its end
     if (nblk > 0) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
         if constexpr (PAGED) {
             int e0[NP];
-            fetch_pages(tbl, pp.page_shift, 0, kend, e0);
-            fetch_pages(tbl, pp.page_shift, kKvBlk, kend, ent);
-            pages_landed(e0, pp.page_stride, pg);
+            fetch(0, e0);
+            fetch(kKvBlk, ent);
+            landed(e0);
         }
-        issue(0, pg, smem);
+        if constexpr (FP8) {
+            load_raw(0, pg, raw);
+            convert_store(raw, 0);
+        } else {
+            issue(0, pg, smem);
+        }
     }
     const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
     for (int j = 0; j < nblk; ++j) {
-        wait_lds_dma();                  // my pieces of block j
+        if constexpr (FP8) stores_landed();   // my part of block j
+        else wait_lds_dma();                  // my pieces of block j
         __builtin_amdgcn_s_barrier();    // everybody's; and everybody has read block j - 1
         asm volatile("" ::: "memory");
         const int par = j & 1;
         if (j + 1 < nblk) {
             if constexpr (PAGED) {
-                pages_landed(ent, pp.page_stride, pg);                              // block j + 1: fetched a block ago
-                fetch_pages(tbl, pp.page_shift, (j + 2) * kKvBlk, kend, ent);       // block j + 2
+                landed(ent);                        // block j + 1: fetched a block ago
+                fetch((j + 2) * kKvBlk, ent);       // block j + 2
             }
-            issue((j + 1) * kKvBlk, pg, smem + (par ^ 1) * C::kStage);
+            if constexpr (FP8) load_raw((j + 1) * kKvBlk, pg, raw);
+            else issue((j + 1) * kKvBlk, pg, smem + (par ^ 1) * C::kStage);
         }
         if (j * kKvBlk < wend) compute(j * kKvBlk, lds0 + par * C::kStage);
+        if constexpr (FP8)   // block j + 1 into the other stage, which everybody left before this block's barrier
+            if (j + 1 < nblk) convert_store(raw, (par ^ 1) * C::kStage);
     }
     mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight
 
@@ -315,6 +438,9 @@ __device__ __forceinline__ void kvp_prefill(const KvpParams& wp)
                 f32x4 acc;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[e] = none ? 0.0f : o[nb][db][4 * g + e] / l;
+                if constexpr (FP8)   // once, behind the quotient: a constant V comes out as exactly v_scale x it
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] *= wp.v_scale;
                 const int col = db * 32 + 8 * g + 4 * hi;
                 if (OUT_F32) {
                     *(f32x4*)((float*)p.o + prow * D + col) = acc;

@@ -23,9 +23,9 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvp8, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
-__all__ = ["forward", "forward_kv", "forward_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
+__all__ = ["forward", "forward_kv", "forward_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "prefill_kv_fp8", "prefill_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
            "SUPPORTED_HEAD_DIMS", "KV_HEAD_DIMS"]
 
@@ -425,8 +425,10 @@ def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: in
 PREFILL_HEAD_DIM = 128   # the one head dim of the chunked-prefill kernels (include/flashattn_amd_kvp.h)
 
 
-def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_lse, out, out_dtype):
-    """The call of a chunked-prefill entry: ``_run`` without a window, scales or a workspace (the kernel has no key split)."""
+def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_lse, out, out_dtype, scales=()):
+    """The call of a chunked-prefill entry: ``_run`` without a window or a workspace (the kernel has no key split); ``scales`` is the fp8 pair
+    (the library of ``include/flashattn_amd_kvp8.h``) or () (that of ``include/flashattn_amd_kvp.h``)."""
+    mod = _cabi_kvp8 if scales else _cabi_kvp
     if q.shape[-1] != PREFILL_HEAD_DIM:
         raise ValueError(f"head_dim {q.shape[-1]} not supported by {fn} ({PREFILL_HEAD_DIM}; forward_{fn[8:]} takes {KV_HEAD_DIMS} and {KV_WIDE_HEAD_DIM})")
     index = q.device.index
@@ -434,9 +436,9 @@ def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_ls
         dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
         out, lse, _ = _out_lse_workspace(q, out, out_dtype, return_lse, None, 0)
         stream = torch.cuda.current_stream(index).cuda_stream
-        rc = getattr(_cabi_kvp.lib(), forward)(q.data_ptr(), *cache, out.data_ptr(), lse.data_ptr() if lse is not None else None, *dims,
-                                               float(scale), int(bool(causal)), dt, ctypes.c_void_p(stream))
-    _cabi_kvp.check(rc)
+        rc = getattr(mod.lib(), forward)(q.data_ptr(), *cache, out.data_ptr(), lse.data_ptr() if lse is not None else None, *dims,
+                                         float(scale), *map(float, scales), int(bool(causal)), dt, ctypes.c_void_p(stream))
+    mod.check(rc)
     return (out, lse) if return_lse else out
 
 
@@ -452,7 +454,7 @@ def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     ``BHkv * ceil(group * nq / 256)`` workgroups are fewer than the 256 CUs leaves CUs idle.  Which to call (``docs/kv_prefill.md``, measured
     at ``BHkv = 8``, ``nk = 8192``): ``prefill_kv`` is 1.2 - 1.3x faster at ``group * nq = 8192`` (one workgroup per CU) and 1.4x SLOWER at
     ``group * nq = 4096`` (half the CUs); the crossover is near ``group * nq = 6000`` there, i.e. ``BHkv * group * nq`` of about 48 000 packed
-    rows.  Below it call ``forward_kv``.  No ``window_left``, no fp8 caches, no other head dim.
+    rows.  Below it call ``forward_kv``.  No ``window_left``, no other head dim; fp8 caches: ``prefill_kv_fp8``.
     """
     q, k, v, _, dims = _contiguous_cache(_BF16, q, k, v, kv_len, kv_lens)
     return _run_prefill("prefill_kv", "fa_kvp_forward", q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype)
@@ -513,6 +515,40 @@ def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
     window_left = _window(window_left)
     q, cache, shape = _paged_cache(_FP8, q, k_pool8, v_pool8, block_table, kv_len, seq_lens)
     return _run(_FP8, True, window_left, q, (ctypes.byref(cache),), shape, shape, scale, (k_scale, v_scale), causal, return_lse, out, out_dtype, workspace)
+
+
+def prefill_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
+                   kv_len: Optional[int] = None, kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False,
+                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+    """``prefill_kv`` over a cache of 8-bit floats (``include/flashattn_amd_kvp8.h``): chunked prefill against the cache ``forward_kv_fp8``
+    decodes from, ``d = 128``.
+
+    ``k8``, ``v8``, ``k_scale``, ``v_scale`` are ``forward_kv_fp8``'s (``torch.float8_e4m3fn``; ``torch.uint8`` is rejected: ``.view`` it; one
+    positive float per tensor and call, ``k_scale`` folded into ``scale`` as one fp32 product, ``v_scale`` applied once to the normalised result,
+    the LSE without it); everything else is ``prefill_kv``'s.  The kernel is ``prefill_kv``'s with other data movement: each 64-key block is
+    loaded, converted to bf16 exactly and written to LDS once per 256 packed rows, where ``forward_kv_fp8`` converts the whole slab once per 32
+    rows.  With ``v_scale`` a power of two the result is bit for bit
+    ``v_scale * prefill_kv(q, k8.to(bfloat16), v8.to(bfloat16), scale=fp32(scale * k_scale))``, and the LSE is that call's for any ``v_scale``.
+    Rows at or beyond a length are never read and may hold the NaN codes.  Which to call (``docs/kv_prefill_fp8.md``, measured at
+    ``BHkv = 8``): ``prefill_kv_fp8`` is 1.15 - 1.4x faster than ``forward_kv_fp8`` at ``group * nq = 8192`` (one workgroup per CU; ``nk`` 2048
+    to 32768, contiguous and paged) and 1.6x SLOWER at ``group * nq = 4096``; the crossover, interpolated, is near ``group * nq = 6500``
+    there.  Call this entry when ``BHkv * ceil(group * nq / 256) >= 256``, ``forward_kv_fp8`` below.  It takes 1.04 - 1.07x the time of
+    ``prefill_kv`` on the dequantised cache.  No ``window_left``, no other head dim.
+    """
+    q, k8, v8, _, dims = _contiguous_cache(_FP8, q, k8, v8, kv_len, kv_lens)
+    return _run_prefill("prefill_kv_fp8", "fa_kvp8_forward", q, (k8.data_ptr(), v8.data_ptr()), dims, scale, causal, return_lse, out, out_dtype,
+                        (k_scale, v_scale))
+
+
+def prefill_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
+                      k_scale: float = 1.0, v_scale: float = 1.0, seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None,
+                      scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+    """``prefill_kv_fp8`` over paged pools of 8-bit floats: ``forward_paged_fp8``'s arguments and rules (pools never copied, strides multiples
+    of 16 elements, pages of 16 .. 65536 rows, table and ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read)
+    on the chunked-prefill kernel, ``d = 128``.  The result is ``prefill_kv_fp8``'s on the gathered bytes, bit for bit."""
+    q, cache, shape = _paged_cache(_FP8, q, k_pool8, v_pool8, block_table, kv_len, seq_lens)
+    return _run_prefill("prefill_paged_fp8", "fa_kvp8_paged_forward", q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype,
+                        (k_scale, v_scale))
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:
