@@ -169,6 +169,24 @@ class Arena:
                 self._fill(b.start + s * slab_bytes, b.start + (s + 1) * slab_bytes, b.dtype, mode, gen)
 
 
+    def fill_input_guards_e4m3(self, names: Sequence[str], seed: int) -> None:
+        """The "finite" surroundings of buffers of 8-bit floats: the guards before and after the input buffers `names` get random bytes from
+        `seed`, none of them an e4m3 NaN code (mode "finite" above draws floats, which a byte buffer cannot take)."""
+        gen = torch.Generator(device=self.raw.device).manual_seed(seed)
+        for name in names:
+            b = self.bufs[name]
+            assert b.kind == "in"
+            for lo, hi in (b.before, b.after):
+                self.raw[lo:hi].copy_(finite_e4m3_bytes(hi - lo, self.raw.device, gen))
+
+
+def finite_e4m3_bytes(n: int, device, gen: Optional[torch.Generator] = None) -> torch.Tensor:
+    """n random bytes, each a finite e4m3fn code (0x7F / 0xFF, the NaNs, become 0x38 = 1.0)"""
+    b = torch.randint(0, 256, (n,), device=device, generator=gen, dtype=torch.int32).to(torch.uint8)
+    b[(b & 0x7F) == 0x7F] = 0x38
+    return b
+
+
 def fill_bytes(t: torch.Tensor, byte: int) -> None:
     """Every byte of a contiguous tensor (0xFF: NaN in fp32 and in bf16)."""
     t.view(torch.uint8).fill_(byte)

@@ -141,6 +141,22 @@ def test_input_fills_are_nan_or_finite(in_dtype):
     assert a.guards_intact()                                      # filling the input side leaves the output side alone
 
 
+def test_e4m3_guard_fill_is_finite_codes_from_the_seed_and_touches_the_named_guards_only():
+    a = ar.Arena([ar.Buf("q", "in", torch.bfloat16, (2, 8), "tensor", 16), ar.Buf("k", "in", torch.uint8, (2, 128), "tensor", 128),
+                  ar.Buf("o", "out", torch.float32, (2, 8), "tensor", 32)], "cpu")
+    a.fill_input_surroundings("nan")
+    a.view("k").fill_(7)
+    a.fill_input_guards_e4m3(("k",), seed=3)
+    b = a.bufs["k"]
+    g = torch.cat([a.raw[lo:hi] for lo, hi in (b.before, b.after)])
+    assert not bool(((g & 0x7F) == 0x7F).any()) and torch.isfinite(g.view(torch.float8_e4m3fn).float()).all() and len(g.unique()) == 254
+    assert bool((a.view("k") == 7).all()) and bool((a.raw[slice(*a.bufs["q"].after)] == 0xFF).all()) and a.guards_intact()
+    a.fill_input_guards_e4m3(("k",), seed=3)
+    assert torch.equal(g, torch.cat([a.raw[lo:hi] for lo, hi in (b.before, b.after)]))                    # the seed decides
+    a.fill_input_guards_e4m3(("k",), seed=4)
+    assert not torch.equal(g, torch.cat([a.raw[lo:hi] for lo, hi in (b.before, b.after)]))
+
+
 def test_isolation_comparison_passes_a_kernel_that_stays_inside_its_slab():
     clean, run_a, run_b = run_abc(make(), None)
     assert ar.isolation_failures(clean, run_a, run_b) == []
