@@ -2,7 +2,7 @@
 // (fa_kvp_prefill.hip instantiates it eight times).  The compute-bound twin of the decode loop (fa_kv_decode16_body.h): the same packed rows,
 // the same masks, the same arithmetic, the opposite split of the work.  No counterpart in the reference.
 // With FP8 = true it is the kernel of libflashattn_amd_kvp8.so over a cache of e4m3 bytes (fa_kvp8_prefill.hip; "FP8" below and Kvp8Map).
-// Out of scope: window_left, d = 64 / 256, a key split for tiny grids, routing from fa_kv_forward.
+// Out of scope: window_left, d = 64 (d = 256: fa_kvp256_prefill_loop.h), a key split for tiny grids, routing from fa_kv_forward.
 //
 // Work split.  A workgroup of four waves owns (K/V slab, 256-row tile of the slab's packed rows); wave w takes rows 64 w .. 64 w + 63 of the
 // tile as two 32-row blocks (nb = 0, 1).  All four waves walk the SAME 64-key blocks, from key 0 to the tile's kend = min(len, diag + imax + 1):

@@ -23,7 +23,7 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvp8, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvp8, _cabi_kvp256, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "prefill_kv_fp8", "prefill_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -422,15 +422,27 @@ def workspace_bytes_paged(batch: int, heads_kv: int, group: int, nq: int, nk: in
                            _OUT_BF16.get(out_dtype, _cabi.FA_DTYPE_BF16_OUT_F32), () if window_left is None else (window_left,))
 
 
-PREFILL_HEAD_DIM = 128   # the one head dim of the chunked-prefill kernels (include/flashattn_amd_kvp.h)
+PREFILL_HEAD_DIM = 128   # the head dim of the fp8 chunked-prefill kernels (include/flashattn_amd_kvp8.h) and of include/flashattn_amd_kvp.h
+# the bf16 chunked-prefill libraries by head dim: (binding, prefix of its entries)
+PREFILL_LIBS = {PREFILL_HEAD_DIM: (_cabi_kvp, "fa_kvp_"), KV_WIDE_HEAD_DIM: (_cabi_kvp256, "fa_kvp256_")}
 
 
-def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_lse, out, out_dtype, scales=()):
+def _prefill_entry(fn: str, d: int, fp8: bool, paged: bool):
+    """(binding, name of the forward) of the chunked-prefill kernel for head dim ``d``; ``fn`` is the front-end entry that asks"""
+    if fp8 and d == PREFILL_HEAD_DIM:
+        return _cabi_kvp8, "fa_kvp8_paged_forward" if paged else "fa_kvp8_forward"
+    if fp8 or d not in PREFILL_LIBS:
+        dims = (PREFILL_HEAD_DIM,) if fp8 else tuple(PREFILL_LIBS)
+        raise ValueError(f"head_dim {d} not supported by {fn} (choose from {dims}; forward_{fn[8:]} takes {KV_HEAD_DIMS} and {KV_WIDE_HEAD_DIM})")
+    mod, prefix = PREFILL_LIBS[d]
+    return mod, prefix + ("paged_forward" if paged else "forward")
+
+
+def _run_prefill(fn: str, paged: bool, q, cache, dims, scale, causal, return_lse, out, out_dtype, scales=()):
     """The call of a chunked-prefill entry: ``_run`` without a window or a workspace (the kernel has no key split); ``scales`` is the fp8 pair
-    (the library of ``include/flashattn_amd_kvp8.h``) or () (that of ``include/flashattn_amd_kvp.h``)."""
-    mod = _cabi_kvp8 if scales else _cabi_kvp
-    if q.shape[-1] != PREFILL_HEAD_DIM:
-        raise ValueError(f"head_dim {q.shape[-1]} not supported by {fn} ({PREFILL_HEAD_DIM}; forward_{fn[8:]} takes {KV_HEAD_DIMS} and {KV_WIDE_HEAD_DIM})")
+    (the library of ``include/flashattn_amd_kvp8.h``) or () (``include/flashattn_amd_kvp.h`` at ``d = 128``, ``include/flashattn_amd_kvp256.h``
+    at ``d = 256``)."""
+    mod, forward = _prefill_entry(fn, q.shape[-1], bool(scales), paged)
     index = q.device.index
     with torch.cuda.device(index):
         dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
@@ -445,7 +457,8 @@ def _run_prefill(fn: str, forward: str, q, cache, dims, scale, causal, return_ls
 def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
                kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None,
                out_dtype: Optional[torch.dtype] = None):
-    """``forward_kv`` for MANY query rows (``include/flashattn_amd_kvp.h``): chunked prefill against a K/V cache, ``d = 128``, bfloat16.
+    """``forward_kv`` for MANY query rows: chunked prefill against a K/V cache, bfloat16, ``d = 128`` (``include/flashattn_amd_kvp.h``) or
+    ``d = 256`` (``include/flashattn_amd_kvp256.h``; its paragraph is the last).
 
     Arguments, masking (``causal`` bottom-right aligned), ``kv_len`` / ``kv_lens`` (read on the device only), rows without a visible key,
     output dtypes, arithmetic and accuracy are ``forward_kv``'s; the results agree with it to that accuracy, not bit for bit.  The kernel is the
@@ -454,20 +467,25 @@ def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     ``BHkv * ceil(group * nq / 256)`` workgroups are fewer than the 256 CUs leaves CUs idle.  Which to call (``docs/kv_prefill.md``, measured
     at ``BHkv = 8``, ``nk = 8192``): ``prefill_kv`` is 1.2 - 1.3x faster at ``group * nq = 8192`` (one workgroup per CU) and 1.4x SLOWER at
     ``group * nq = 4096`` (half the CUs); the crossover is near ``group * nq = 6000`` there, i.e. ``BHkv * group * nq`` of about 48 000 packed
-    rows.  Below it call ``forward_kv``.  No ``window_left``, no other head dim; fp8 caches: ``prefill_kv_fp8``.
+    rows.  Below it call ``forward_kv``.  No ``window_left``, no other head dim; fp8 caches: ``prefill_kv_fp8`` (``d = 128`` only).
+
+    ``d = 256`` runs a kernel of its own with the same contract: a workgroup owns 128 packed rows (one 32-row block per wave), so the grid is
+    ``BHkv * ceil(group * nq / 128)``.  Measured (``docs/kv_prefill_d256.md``, ``BHkv = 8``, group 4, causal): 0.43 - 0.58 of ``forward_kv``'s
+    time at 256 and 512 workgroups (``nq`` 1024 and 2048, ``nk`` 2048 to 32768), 2.2x SLOWER at 64 workgroups; its time is flat up to one
+    workgroup per CU while ``forward_kv``'s grows with the rows, and the two meet, interpolated, near 150 workgroups.  Call it from there on.
     """
     q, k, v, _, dims = _contiguous_cache(_BF16, q, k, v, kv_len, kv_lens)
-    return _run_prefill("prefill_kv", "fa_kvp_forward", q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype)
+    return _run_prefill("prefill_kv", False, q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype)
 
 
 def prefill_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
                   seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None, scale: float = 1.0, return_lse: bool = False,
                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
     """``prefill_kv`` over a paged cache: ``forward_paged``'s arguments and rules (pools never copied, pages of 16 .. 65536 rows, table and
-    ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read) on the chunked-prefill kernel, ``d = 128``.  The
-    result is ``prefill_kv``'s on the gathered cache, bit for bit."""
+    ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read) on the chunked-prefill kernel, ``d = 128`` or
+    ``d = 256`` (``prefill_kv`` says which library runs).  The result is ``prefill_kv``'s on the gathered cache, bit for bit."""
     q, cache, shape = _paged_cache(_BF16, q, k_pool, v_pool, block_table, kv_len, seq_lens)
-    return _run_prefill("prefill_paged", "fa_kvp_paged_forward", q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype)
+    return _run_prefill("prefill_paged", True, q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype)
 
 
 def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
@@ -536,7 +554,7 @@ def prefill_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
     ``prefill_kv`` on the dequantised cache.  No ``window_left``, no other head dim.
     """
     q, k8, v8, _, dims = _contiguous_cache(_FP8, q, k8, v8, kv_len, kv_lens)
-    return _run_prefill("prefill_kv_fp8", "fa_kvp8_forward", q, (k8.data_ptr(), v8.data_ptr()), dims, scale, causal, return_lse, out, out_dtype,
+    return _run_prefill("prefill_kv_fp8", False, q, (k8.data_ptr(), v8.data_ptr()), dims, scale, causal, return_lse, out, out_dtype,
                         (k_scale, v_scale))
 
 
@@ -547,7 +565,7 @@ def prefill_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
     of 16 elements, pages of 16 .. 65536 rows, table and ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read)
     on the chunked-prefill kernel, ``d = 128``.  The result is ``prefill_kv_fp8``'s on the gathered bytes, bit for bit."""
     q, cache, shape = _paged_cache(_FP8, q, k_pool8, v_pool8, block_table, kv_len, seq_lens)
-    return _run_prefill("prefill_paged_fp8", "fa_kvp8_paged_forward", q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype,
+    return _run_prefill("prefill_paged_fp8", True, q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype,
                         (k_scale, v_scale))
 
 
