@@ -8,7 +8,7 @@ hipcc cross-compiles for gfx950 without a GPU present.
 
     python flashattention.c_amd/build.py [--force] [--jobs N] [--ablation] [--torch-binding]
 
-The ten KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
+The eleven KV-cache extension libraries (``libflashattn_amd_<tag>.so`` behind ``include/flashattn_amd_<tag>.h``; ``EXT_LIBS`` names them and their
 sources) are always built beside it.
 ``--ablation`` additionally builds ``libflashattn_amd_ablation.so`` (+ ``fa_driver_ablation``): the same sources compiled with
 ``-DFA_ABLATION=1`` plus the timing-only ablation instantiations quoted in DESIGN.md section 4 (results are garbage by design).
@@ -64,6 +64,7 @@ ABL_LIB_PATH = os.path.join(PKG_DIR, "libflashattn_amd_ablation.so")
 # the turn of the library it belongs to, and its OBJECT is linked into each.  No library exports a symbol of another: what else they share (plan,
 # decode loop, validator) is inline in csrc/fa_kv*.h.
 EXT_LIBS = {
+    "kvpw": ["fa_kvpw8_prefill.hip", "fa_kvpw_prefill.hip", "fa_kvpw256_prefill.hip", "fa_kvpw_host.cpp"],  # the three prefill loops under a sliding window (WINDOW = true)
     "kvp256": ["fa_kvp256_prefill.hip", "fa_kvp256_host.cpp"],                  # chunked prefill over the bf16 caches at d = 256: 128-row tiles, a 512-byte-pitch K image
     "kvp8": ["fa_kvp8_prefill.hip", "fa_kvp8_host.cpp"],                        # chunked prefill over the fp8 caches at d = 128: the kvp loop, blocks converted on their way into LDS
     "kvp": ["fa_kvp_prefill.hip", "fa_kvp_host.cpp"],                           # chunked prefill over the bf16 caches at d = 128: 256-row tiles, K/V through LDS, no merge kernel
@@ -99,6 +100,8 @@ EXTRA_FLAGS["fa_kv8_256_decode.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]   # th
 EXTRA_FLAGS["fa_kvp_prefill.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]      # ... of 160 registers, and the softmax of 64 rows per wave beside the matrix pipe
 EXTRA_FLAGS["fa_kvp8_prefill.hip"] = EXTRA_FLAGS["fa_kvp_prefill.hip"]      # the same loop
 EXTRA_FLAGS["fa_kvp256_prefill.hip"] = EXTRA_FLAGS["fa_kv256_decode.hip"]   # the d = 256 rescale (144 registers) beside the matrix pipe, in the prefill loop
+for _u in ("fa_kvpw_prefill.hip", "fa_kvpw8_prefill.hip", "fa_kvpw256_prefill.hip"):   # the same loops with WINDOW = true
+    EXTRA_FLAGS[_u] = EXTRA_FLAGS["fa_kv256_decode.hip"]
 
 
 def hipcc() -> str:
@@ -152,7 +155,7 @@ def _build_driver(out: str, lib_path: str, libname: str, force: bool) -> None:
 def build(force: bool = False, jobs: int = 8, verbose: bool = False, ablation: bool = False, torch_binding: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        # one pool for all eleven libraries: the extension libraries' sources first (each distinct one once), then the product's
+        # one pool for all twelve libraries: the extension libraries' sources first (each distinct one once), then the product's
         ext_futs = {s: ex.submit(_compile, s, force) for tag, srcs in EXT_LIBS.items() for s in srcs if SHARED_OBJECTS.get(s, tag) == tag}
         objs = list(ex.map(lambda s: _compile(s, force), LIB_SOURCES))
         ext_objs = {tag: [ext_futs[s].result() for s in srcs] for tag, srcs in EXT_LIBS.items()}

@@ -2,7 +2,7 @@
 // of the chunked-prefill kernels and their launcher.  The library is the KV-cache forward of fa_kv.h / fa_paged.h for MANY query rows at
 // d = 128: validation and the fill of the parameters are fa_kv_host.h's (the unsplit plan: there is no key split here and no workspace), the
 // kernel is its own (fa_kvp_prefill_loop.h), because the decode loop re-reads the K/V slab once per 32 rows.
-// Out of scope: window_left (fp8 caches: fa_kvp8.h, libflashattn_amd_kvp8.so), d = 64 (d = 256: fa_kvp256.h, libflashattn_amd_kvp256.so), a key split for tiny grids, routing from fa_kv_forward.
+// Under a sliding window: fa_kvpw.h, libflashattn_amd_kvpw.so.  Out of scope (fp8 caches: fa_kvp8.h, libflashattn_amd_kvp8.so): d = 64 (d = 256: fa_kvp256.h, libflashattn_amd_kvp256.so), a key split for tiny grids, routing from fa_kv_forward.
 #pragma once
 #include "fa_paged.h"
 

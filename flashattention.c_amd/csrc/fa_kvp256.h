@@ -2,7 +2,7 @@
 // parameters of the chunked-prefill kernels at head dim 256 and their launcher.  The library is fa_kvp.h's at d = 256: validation and the fill
 // of the parameters are fa_kv_host.h's (the unsplit plan: no key split, no workspace), the kernel is its own (fa_kvp256_prefill_loop.h),
 // because the two row blocks per wave of fa_kvp_prefill_loop.h alone would fill the accumulation half of the register file at this width.
-// Out of scope: window_left, fp8 caches, a key split for tiny grids, routing from fa_kv256_forward.
+// Under a sliding window: fa_kvpw.h, libflashattn_amd_kvpw.so.  Out of scope: fp8 caches, a key split for tiny grids, routing from fa_kv256_forward.
 #pragma once
 #include "fa_paged.h"
 

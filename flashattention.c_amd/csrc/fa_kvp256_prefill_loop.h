@@ -1,7 +1,8 @@
 // fa_kvp256_prefill_loop.h -- chunked prefill over a bf16 cache at head dim 256, contiguous or paged: the kernel of libflashattn_amd_kvp256.so
 // (fa_kvp256_prefill.hip instantiates it eight times).  The d = 256 twin of fa_kvp_prefill_loop.h: the same packed rows, masks, arithmetic
 // and one-barrier protocol, with a work split, an LDS map and a register plan of its own.  No counterpart in the reference.
-// Out of scope: window_left, fp8 caches, a key split for tiny grids, routing from fa_kv256_forward.
+// With WINDOW = true it is the d = 256 kernel of libflashattn_amd_kvpw.so (fa_kvpw256_prefill.hip; "WINDOW" in fa_kvp_prefill_loop.h says what
+// changes: the same here).  Out of scope: fp8 caches, a key split for tiny grids, routing from fa_kv256_forward.
 //
 // Work split.  A workgroup of four waves owns (K/V slab, 128-row tile of the slab's packed rows); wave w takes rows 32 w .. 32 w + 31 of the
 // tile as ONE 32-row MFMA column block (the d = 128 loop: two; O for two would be 2 x 128 registers, the whole accumulation half).  All four
@@ -99,8 +100,8 @@ __device__ __forceinline__ void kvp256_read_v(unsigned va, s16x4 (&vv)[2 * Kvp25
     ((vv[2 * I] = lds_read_tr16_at<C::kImage + 2 * (DB0 + I) * 128>(va), vv[2 * I + 1] = lds_read_tr16_at<C::kImage + 2 * C::kKeyGroup + 2 * (DB0 + I) * 128>(va)), ...);
 }
 
-template <bool CAUSAL, bool OUT_F32, bool PAGED>
-__device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
+template <bool CAUSAL, bool OUT_F32, bool PAGED, bool WINDOW = false>
+__device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp, int window_left = 0)
 {
     using C = Kvp256Cfg;
     constexpr int D = C::D, KS = C::KS, DB = C::DB, NP = kPagedBlockPages, VC = C::kVChunk;
@@ -141,11 +142,24 @@ __device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
     const int kend = keys_of(row0, kKvp256RowTile);
     const int wend = __builtin_amdgcn_readfirstlane(keys_of(wrow0, kKvRowTile));   // this wave's rows see nothing at or beyond it
     const int nblk = (kend + kKvBlk - 1) / kKvBlk;
+    // WINDOW, as in fa_kvp_prefill_loop.h: the tile's lowest visible key lo (the lower clamp of every row loaded or looked up; kend > lo
+    // wherever kend >= 1), its block jbeg, where the walk starts, and the wave's lowest visible key wbeg
+    int lo = 0, jbeg = 0, wbeg = 0;
+    if constexpr (WINDOW) {
+        auto first_key_of = [&](int r0, int rows) {
+            const int rl = min(r0 + rows - 1, M - 1);
+            return max(diag + ((r0 / nq != rl / nq) ? 0 : r0 % nq) - window_left, 0);
+        };
+        lo = first_key_of(row0, kKvp256RowTile);
+        jbeg = lo / kKvBlk;
+        wbeg = __builtin_amdgcn_readfirstlane(first_key_of(wrow0, kKvRowTile));   // read only where wend > 0, i.e. wrow0 < M
+    }
 
     // ---- Q, the mask ----
     const bool row_ok = wrow0 + lq < M;
-    int lim = kend - 1;
+    int lim = kend - 1, lo_row = 0;
     if (CAUSAL) lim = min(lim, diag + (wrow0 + lq) % nq);
+    if constexpr (WINDOW) lo_row = diag + (wrow0 + lq) % nq - window_left;   // the first key this lane's row sees
     bf16x8 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = kv_q_fragment<D>(p.q, (int64_t)slab * M + min(wrow0, M - 1), row_ok, lq, hi, ks);
@@ -183,7 +197,8 @@ __device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
         for (int i = 0; i < C::kPieces; ++i) {
             constexpr int kHalf = D / 2;
             const int g = i >> 1, b = i & 1;
-            const int kr = min(kv0 + 16 * g + 2 * b + k_row, kend - 1), vr = min(kv0 + 16 * g + v_row, kend - 1);
+            int kr = min(kv0 + 16 * g + 2 * b + k_row, kend - 1), vr = min(kv0 + 16 * g + v_row, kend - 1);
+            if constexpr (WINDOW) kr = max(kr, lo), vr = max(vr, lo);   // the walk's first block may begin below lo
             const unsigned kc = (unsigned)(k_colb ^ (32 * b)), vc = (unsigned)(b * kHalf + v_col) * 2u;
             const char *ks, *vs;
             if constexpr (PAGED) {
@@ -227,11 +242,20 @@ __device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
 #pragma unroll
         for (int j = 0; j < 8; ++j) ka[j] = stage + k_lane_off + ((32 * j) ^ k_swz);
         const bool second = kv0 + 32 < wend;   // wave-uniform: the wave's rows see something of the second 32 keys
+        bool first = true;                     // ... and of the first (WINDOW: not where they lie below the wave's window; `second` holds then)
+        if constexpr (WINDOW) {
+            first = kv0 + 32 > wbeg;
+            if (!first)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ka[j] += 32 * C::kRowBytes;
+        }
         bf16x8 kf[KS];
         kvp256_read_k(ka, kf, kAllKs);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && !second) break;
+            if constexpr (WINDOW)
+                if (h == 0 && !first) continue;
             // ---- S^T = K Q^T ----
             f32x16 s;
 #pragma unroll
@@ -246,7 +270,7 @@ __device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
 
             // ---- online softmax ----
             bf16x8 ph[2], pl[2];
-            const KvRescale rs = kv256_mask_and_max<false>(s, lim - kv0 - 32 * h - 4 * hi, c, m, 0);
+            const KvRescale rs = kv256_mask_and_max<WINDOW>(s, lim - kv0 - 32 * h - 4 * hi, c, m, lo_row - kv0 - 32 * h - 4 * hi);
             if (__builtin_amdgcn_ballot_w64(rs.alpha != 1.0f) != 0) {   // some row's maximum moved
 #pragma unroll
                 for (int db = 0; db < DB; ++db)
@@ -297,26 +321,28 @@ __device__ __forceinline__ void kvp256_prefill(const Kvp256Params& wp)
     if (nblk > 0) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
         if constexpr (PAGED) {
             int e0[NP];
-            fetch_pages(tbl, pp.page_shift, 0, kend, e0);
-            fetch_pages(tbl, pp.page_shift, kKvBlk, kend, ent);
+            fetch_pages<WINDOW>(tbl, pp.page_shift, jbeg * kKvBlk, kend, e0, lo);
+            fetch_pages<WINDOW>(tbl, pp.page_shift, (jbeg + 1) * kKvBlk, kend, ent, lo);
             pages_landed(e0, pp.page_stride, pg);
         }
-        issue(0, pg, smem);
+        issue(jbeg * kKvBlk, pg, smem);
     }
     const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-    for (int j = 0; j < nblk; ++j) {
+    for (int j = jbeg; j < nblk; ++j) {   // WINDOW: from the block of the tile's lowest key on (jbeg = 0 otherwise)
         wait_lds_dma();                  // my pieces of block j
         __builtin_amdgcn_s_barrier();    // everybody's; and everybody has read block j - 1
         asm volatile("" ::: "memory");
-        const int par = j & 1;
+        const int par = (j - jbeg) & 1;   // the stages alternate from the walk's first block on
         if (j + 1 < nblk) {
             if constexpr (PAGED) {
                 pages_landed(ent, pp.page_stride, pg);                        // block j + 1: fetched a block ago
-                fetch_pages(tbl, pp.page_shift, (j + 2) * kKvBlk, kend, ent);   // block j + 2
+                fetch_pages<WINDOW>(tbl, pp.page_shift, (j + 2) * kKvBlk, kend, ent, lo);   // block j + 2
             }
             issue((j + 1) * kKvBlk, pg, smem + (par ^ 1) * C::kStage);
         }
-        if (j * kKvBlk < wend) compute(j * kKvBlk, lds0 + par * C::kStage);
+        bool mine = j * kKvBlk < wend;
+        if constexpr (WINDOW) mine = mine && (j + 1) * kKvBlk > wbeg;   // ... nor is the block wholly below the wave's window
+        if (mine) compute(j * kKvBlk, lds0 + par * C::kStage);
     }
     mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight
 

@@ -2,7 +2,8 @@
 // (fa_kvp_prefill.hip instantiates it eight times).  The compute-bound twin of the decode loop (fa_kv_decode16_body.h): the same packed rows,
 // the same masks, the same arithmetic, the opposite split of the work.  No counterpart in the reference.
 // With FP8 = true it is the kernel of libflashattn_amd_kvp8.so over a cache of e4m3 bytes (fa_kvp8_prefill.hip; "FP8" below and Kvp8Map).
-// Out of scope: window_left, d = 64 (d = 256: fa_kvp256_prefill_loop.h), a key split for tiny grids, routing from fa_kv_forward.
+// With WINDOW = true it is the d = 128 kernel (either cache type) of libflashattn_amd_kvpw.so (fa_kvpw_prefill.hip, fa_kvpw8_prefill.hip; "WINDOW" below).
+// Out of scope: d = 64 (d = 256: fa_kvp256_prefill_loop.h), a key split for tiny grids, routing from fa_kv_forward.
 //
 // Work split.  A workgroup of four waves owns (K/V slab, 256-row tile of the slab's packed rows); wave w takes rows 64 w .. 64 w + 63 of the
 // tile as two 32-row blocks (nb = 0, 1).  All four waves walk the SAME 64-key blocks, from key 0 to the tile's kend = min(len, diag + imax + 1):
@@ -50,6 +51,14 @@
 // and drained by the lgkmcnt(0) in front of the barrier, so none is outstanding while lds_landed_but counts reads; the paged scalar loads sit
 // where the bf16 kernel has them, between the barrier and the compute, and an entry in flight only makes a counted wait stricter (above).  A
 // wave's two loads of a block lie in one 16-row group each (2 i + wave / 2), so it fetches two entries per block, not four.
+//
+// WINDOW (one text again: everything it adds sits behind `if constexpr (WINDOW)`, and with WINDOW = false the code objects are what they
+// were).  Query i sees no key below diag + i - window_left (include/flashattn_amd_kvw.h; window_left travels beside the parameter struct).
+// A tile has a lower end lo beside kend -- the first key of its lowest row -- and walks the blocks lo / 64 .. nblk - 1: prologue, stage
+// parity and table fetches count from there.  Rows of the first block below lo are redirected to lo as rows at or beyond kend are to kend - 1,
+// on the logical row and before the table lookup, so nothing below lo is read; the mask is kv256_mask_and_max<true> with the lane's lower
+// bound; and a wave skips the matrix work of a block, or of its first 32 keys, that lies wholly below its own rows' first key wbeg, as it
+// does above wend.  The tile order stays: under a window the tiles weigh nearly the same.
 #pragma once
 #include "fa_kv256_decode_loop.h"
 #include "fa_kv8_decode_core.h"
@@ -91,11 +100,14 @@ struct Kvp8Map {
 
 // fetch_pages / pages_landed of fa_kv_decode_core.h for the two loads of a wave: rows row0 and row0 + kRowsPerLoad of the block, clamped to
 // kend - 1 BEFORE the lookup (only called with kend >= 1)
-__device__ __forceinline__ void kvp8_fetch_pages(cst_i32_t* tbl, int page_shift, int row0, int kend, int (&e)[Kvp8Map::kLoads])
+template <bool WINDOW = false>
+__device__ __forceinline__ void kvp8_fetch_pages(cst_i32_t* tbl, int page_shift, int row0, int kend, int (&e)[Kvp8Map::kLoads], int lo = 0)
 {
 #pragma unroll
     for (int i = 0; i < Kvp8Map::kLoads; ++i) {
-        int idx = __builtin_amdgcn_readfirstlane(min(row0 + i * Kvp8Map::kRowsPerLoad, kend - 1)) >> page_shift;
+        int row = min(row0 + i * Kvp8Map::kRowsPerLoad, kend - 1);
+        if constexpr (WINDOW) row = max(row, lo);
+        int idx = __builtin_amdgcn_readfirstlane(row) >> page_shift;
         asm volatile("" : "+s"(idx));
         e[i] = tbl[idx];
     }
@@ -124,8 +136,8 @@ __device__ __forceinline__ void lds_landed_but(T (&x)[K])
     for (int i = 0; i < K; ++i) asm volatile("" : "+v"(x[i]));
 }
 
-template <bool CAUSAL, bool OUT_F32, bool PAGED, bool FP8 = false, typename Params = KvpParams>
-__device__ __forceinline__ void kvp_prefill(const Params& wp)
+template <bool CAUSAL, bool OUT_F32, bool PAGED, bool FP8 = false, typename Params = KvpParams, bool WINDOW = false>
+__device__ __forceinline__ void kvp_prefill(const Params& wp, int window_left = 0)
 {
     using C = KvpCfg;
     using elem_t = std::conditional_t<FP8, uint8_t, __bf16>;   // FP8: one byte per element, so every offset of the cache is in bytes
@@ -168,10 +180,23 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
     const int kend = keys_of(row0, kKvpRowTile);
     const int wend = __builtin_amdgcn_readfirstlane(keys_of(wrow0, NB * kKvRowTile));   // this wave's rows see nothing at or beyond it
     const int nblk = (kend + kKvBlk - 1) / kKvBlk;
+    // WINDOW: the first key a range of packed rows sees, that of its lowest row (i = 0 where the range straddles a head, as keys_of has
+    // i = nq - 1 there).  lo is the tile's -- kend > lo wherever kend >= 1: the widest row reaches beyond the lowest row's first key -- and
+    // every row that is loaded or looked up is clamped to it from below; the walk starts at lo's block, jbeg; wbeg is the wave's.
+    int lo = 0, jbeg = 0, wbeg = 0;
+    if constexpr (WINDOW) {
+        auto first_key_of = [&](int r0, int rows) {
+            const int rl = min(r0 + rows - 1, M - 1);
+            return max(diag + ((r0 / nq != rl / nq) ? 0 : r0 % nq) - window_left, 0);
+        };
+        lo = first_key_of(row0, kKvpRowTile);
+        jbeg = lo / kKvBlk;
+        wbeg = __builtin_amdgcn_readfirstlane(first_key_of(wrow0, NB * kKvRowTile));   // read only where wend > 0, i.e. wrow0 < M
+    }
 
     // ---- Q, the masks ----
     bf16x8 qf[NB][KS];
-    int lim[NB];
+    int lim[NB], lo_row[NB];
     bool row_ok[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -179,6 +204,11 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
         row_ok[nb] = r0 + lq < M;
         lim[nb] = kend - 1;
         if (CAUSAL) lim[nb] = min(lim[nb], diag + (r0 + lq) % nq);
+        // WINDOW: the first key this lane's row sees.  CAUSAL, it is lim - window_left and is formed from lim in every step (a row of the
+        // slab has i <= the tile's imax, so its lim is diag + i unclipped); otherwise it is held -- FP8, whose vector half is full, in the
+        // accumulation half (q_in_registers)
+        lo_row[nb] = 0;
+        if constexpr (WINDOW && !CAUSAL) lo_row[nb] = diag + (r0 + lq) % nq - window_left;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[nb][ks] = kv_q_fragment<D>(p.q, (int64_t)slab * M + min(r0, M - 1), row_ok[nb], lq, hi, ks);
     }
@@ -190,6 +220,9 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
                 if (nb == 0) asm volatile("" : "+v"(qf[nb][ks]));
                 else asm volatile("" : "+a"(qf[nb][ks]));
             }
+        if constexpr (WINDOW && FP8)   // the lane's bound: lim where both come from it, lo_row beside a uniform lim
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) asm volatile("" : "+a"(CAUSAL ? lim[nb] : lo_row[nb]));
     };
     q_in_registers();
     bf16x8 ones;
@@ -219,7 +252,8 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
         if constexpr (!FP8)
 #pragma unroll
         for (int i = 0; i < C::kPieces; ++i) {
-            const int kr = min(kv0 + 16 * i + k_row, kend - 1), vr = min(kv0 + 16 * i + v_row, kend - 1);
+            int kr = min(kv0 + 16 * i + k_row, kend - 1), vr = min(kv0 + 16 * i + v_row, kend - 1);
+            if constexpr (WINDOW) kr = max(kr, lo), vr = max(vr, lo);   // the walk's first block may begin below lo
             const char *ks, *vs;
             if constexpr (PAGED) {
                 ks = (const char*)(kg + pb[i]) + ((unsigned)(kr & page_mask) * row_stride + k_col) * 2u;
@@ -244,7 +278,8 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
             const int v_key = 8 * wave + 4 * (lane_v >> 5) + ((lane_v >> 1) & 3), v_chunk = (lane_v & 1) + 2 * ((lane_v >> 3) & 3);
 #pragma unroll
             for (int i = 0; i < NL; ++i) {
-                const int kr = min(kv0 + i * Kvp8Map::kRowsPerLoad + k_key, kend - 1), vr = min(kv0 + i * Kvp8Map::kRowsPerLoad + v_key, kend - 1);
+                int kr = min(kv0 + i * Kvp8Map::kRowsPerLoad + k_key, kend - 1), vr = min(kv0 + i * Kvp8Map::kRowsPerLoad + v_key, kend - 1);
+                if constexpr (WINDOW) kr = max(kr, lo), vr = max(vr, lo);
                 const uint8_t *ks, *vs;
                 if constexpr (PAGED) {
                     ks = kg + pb[i] + ((unsigned)(kr & page_mask) * row_stride + k_chunk * 16);
@@ -315,6 +350,8 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && kv0 + 32 >= wend) break;   // the wave's rows see nothing of the second half
+            if constexpr (WINDOW)
+                if (h == 0 && kv0 + 32 <= wbeg) continue;   // ... or, below their window, of the first
             // ---- S^T = K Q^T ----
             bf16x8 kf[KS];
 #pragma unroll
@@ -336,7 +373,8 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
             bf16x8 ph[NB][2], pl[NB][2];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                const KvRescale rs = kv256_mask_and_max<false>(s[nb], lim[nb] - kv0 - 32 * h - 4 * hi, c, m[nb], 0);
+                const KvRescale rs = kv256_mask_and_max<WINDOW>(s[nb], lim[nb] - kv0 - 32 * h - 4 * hi, c, m[nb],
+                                                                   (CAUSAL ? lim[nb] - window_left : lo_row[nb]) - kv0 - 32 * h - 4 * hi);
                 if (__builtin_amdgcn_ballot_w64(rs.alpha != 1.0f) != 0) {   // some row's maximum moved
 #pragma unroll
                     for (int db = 0; db < DB; ++db)
@@ -381,8 +419,8 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
     for (int i = 0; i < NP; ++i) pg[i] = 0, ent[i] = 0;
     // the entries of the block at kv0 (FP8: of this wave's two loads of it), and the point up to which they must have arrived
     auto fetch = [&](int kv0, int(&e)[NP]) {
-        if constexpr (FP8) kvp8_fetch_pages(tbl, pp.page_shift, kv0 + 8 * wave, kend, e);
-        else fetch_pages(tbl, pp.page_shift, kv0, kend, e);
+        if constexpr (FP8) kvp8_fetch_pages<WINDOW>(tbl, pp.page_shift, kv0 + 8 * wave, kend, e, lo);
+        else fetch_pages<WINDOW>(tbl, pp.page_shift, kv0, kend, e, lo);
     };
     auto landed = [&](int(&e)[NP]) {
         if constexpr (FP8) kvp8_pages_landed(e, pp.page_stride, pg);
@@ -392,24 +430,24 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
     if (nblk > 0) {   // kend >= 1 from here on: every row (and, PAGED, every table index) is that of a key below len
         if constexpr (PAGED) {
             int e0[NP];
-            fetch(0, e0);
-            fetch(kKvBlk, ent);
+            fetch(jbeg * kKvBlk, e0);
+            fetch((jbeg + 1) * kKvBlk, ent);
             landed(e0);
         }
         if constexpr (FP8) {
-            load_raw(0, pg, raw);
+            load_raw(jbeg * kKvBlk, pg, raw);
             convert_store(raw, 0);
         } else {
-            issue(0, pg, smem);
+            issue(jbeg * kKvBlk, pg, smem);
         }
     }
     const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-    for (int j = 0; j < nblk; ++j) {
+    for (int j = jbeg; j < nblk; ++j) {   // WINDOW: from the block of the tile's lowest key on (jbeg = 0 otherwise)
         if constexpr (FP8) stores_landed();   // my part of block j
         else wait_lds_dma();                  // my pieces of block j
         __builtin_amdgcn_s_barrier();    // everybody's; and everybody has read block j - 1
         asm volatile("" ::: "memory");
-        const int par = j & 1;
+        const int par = (j - jbeg) & 1;   // the stages alternate from the walk's first block on
         if (j + 1 < nblk) {
             if constexpr (PAGED) {
                 landed(ent);                        // block j + 1: fetched a block ago
@@ -418,19 +456,28 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
             if constexpr (FP8) load_raw((j + 1) * kKvBlk, pg, raw);
             else issue((j + 1) * kKvBlk, pg, smem + (par ^ 1) * C::kStage);
         }
-        if (j * kKvBlk < wend) compute(j * kKvBlk, lds0 + par * C::kStage);
+        bool mine = j * kKvBlk < wend;
+        if constexpr (WINDOW) mine = mine && (j + 1) * kKvBlk > wbeg;   // ... nor is the block wholly below the wave's window
+        if (mine) compute(j * kKvBlk, lds0 + par * C::kStage);
         if constexpr (FP8)   // block j + 1 into the other stage, which everybody left before this block's barrier
             if (j + 1 < nblk) convert_store(raw, (par ^ 1) * C::kStage);
     }
     mfma_drain();   // the loop exit is a branch: the last matrix instructions may still be in flight
 
     // ---- epilogue: every wave stores its own rows.  Lane (lq, hi) holds columns 32 db + 8 g + 4 hi .. + 4 of row lq in o[.][db][4 g ..] ----
+    // (WINDOW over an fp8 cache: the lane's coordinates are derived from its number again, behind an empty statement, as in
+    // fa_kvp256_prefill_loop.h -- held through the loop beside the raw bytes and the lower bound they would not fit)
+    int lq_e = lq, hi_e = hi;
+    if constexpr (WINDOW && FP8) {
+        asm volatile("" : "+v"(lane_v));
+        lq_e = lane_v & 31, hi_e = lane_v >> 5;
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        if (!row_ok[nb]) continue;
+        if ((WINDOW && FP8) ? wrow0 + nb * kKvRowTile + lq_e >= M : !row_ok[nb]) continue;
         const float l = lacc[nb][0];
         const bool none = !(l > 0.0f);   // no visible key: O = 0, LSE = -inf
-        const int64_t prow = (int64_t)slab * M + wrow0 + nb * kKvRowTile + lq;
+        const int64_t prow = (int64_t)slab * M + wrow0 + nb * kKvRowTile + lq_e;
 #pragma unroll
         for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -441,7 +488,7 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
                 if constexpr (FP8)   // once, behind the quotient: a constant V comes out as exactly v_scale x it
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[e] *= wp.v_scale;
-                const int col = db * 32 + 8 * g + 4 * hi;
+                const int col = db * 32 + 8 * g + 4 * hi_e;
                 if (OUT_F32) {
                     *(f32x4*)((float*)p.o + prow * D + col) = acc;
                 } else {
@@ -451,7 +498,7 @@ __device__ __forceinline__ void kvp_prefill(const Params& wp)
                     *(bf16x4*)((__bf16*)p.o + prow * D + col) = r;
                 }
             }
-        if (hi == 0 && p.lse != nullptr) p.lse[prow] = none ? -INFINITY : (m[nb] + __builtin_amdgcn_logf(l)) * kLn2;
+        if (hi_e == 0 && p.lse != nullptr) p.lse[prow] = none ? -INFINITY : (m[nb] + __builtin_amdgcn_logf(l)) * kLn2;
     }
 }
 

@@ -23,7 +23,7 @@ from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
-from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvp8, _cabi_kvp256, _cabi_kvw, _cabi_kvw8, _cabi_paged
+from . import _cabi, _cabi_kv, _cabi_kv8, _cabi_kv8_256, _cabi_kv256, _cabi_kvp, _cabi_kvp8, _cabi_kvp256, _cabi_kvpw, _cabi_kvw, _cabi_kvw8, _cabi_paged
 
 __all__ = ["forward", "forward_kv", "forward_paged", "prefill_kv", "prefill_paged", "forward_kv_fp8", "forward_paged_fp8", "prefill_kv_fp8", "prefill_paged_fp8", "forward_packed_qkv", "load", "time_forward", "last_forward_route", "workspace_bytes", "workspace_bytes_kv",
            "workspace_bytes_paged", "stats",
@@ -438,25 +438,29 @@ def _prefill_entry(fn: str, d: int, fp8: bool, paged: bool):
     return mod, prefix + ("paged_forward" if paged else "forward")
 
 
-def _run_prefill(fn: str, paged: bool, q, cache, dims, scale, causal, return_lse, out, out_dtype, scales=()):
-    """The call of a chunked-prefill entry: ``_run`` without a window or a workspace (the kernel has no key split); ``scales`` is the fp8 pair
+def _run_prefill(fn: str, paged: bool, q, cache, dims, scale, causal, return_lse, out, out_dtype, scales=(), window_left=None):
+    """The call of a chunked-prefill entry: ``_run`` without a workspace (the kernel has no key split); ``scales`` is the fp8 pair
     (the library of ``include/flashattn_amd_kvp8.h``) or () (``include/flashattn_amd_kvp.h`` at ``d = 128``, ``include/flashattn_amd_kvp256.h``
-    at ``d = 256``)."""
+    at ``d = 256``).  ``window_left``: None takes those libraries, an int the one library of ``include/flashattn_amd_kvpw.h``, which serves the
+    same head dims and takes the window behind ``dtype``."""
     mod, forward = _prefill_entry(fn, q.shape[-1], bool(scales), paged)
+    window = ()
+    if window_left is not None:
+        mod, forward, window = _cabi_kvpw, "fa_kvpw_" + ("fp8_" if scales else "") + ("paged_forward" if paged else "forward"), (window_left,)
     index = q.device.index
     with torch.cuda.device(index):
         dt = _OUT_BF16.get(out_dtype if out_dtype is not None else (out.dtype if out is not None else q.dtype), _cabi.FA_DTYPE_BF16_OUT_F32)
         out, lse, _ = _out_lse_workspace(q, out, out_dtype, return_lse, None, 0)
         stream = torch.cuda.current_stream(index).cuda_stream
         rc = getattr(mod.lib(), forward)(q.data_ptr(), *cache, out.data_ptr(), lse.data_ptr() if lse is not None else None, *dims,
-                                         float(scale), *map(float, scales), int(bool(causal)), dt, ctypes.c_void_p(stream))
+                                         float(scale), *map(float, scales), int(bool(causal)), dt, *window, ctypes.c_void_p(stream))
     mod.check(rc)
     return (out, lse) if return_lse else out
 
 
 def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False, *, kv_len: Optional[int] = None,
                kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None,
-               out_dtype: Optional[torch.dtype] = None):
+               out_dtype: Optional[torch.dtype] = None, window_left: Optional[int] = None):
     """``forward_kv`` for MANY query rows: chunked prefill against a K/V cache, bfloat16, ``d = 128`` (``include/flashattn_amd_kvp.h``) or
     ``d = 256`` (``include/flashattn_amd_kvp256.h``; its paragraph is the last).
 
@@ -467,25 +471,38 @@ def prefill_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool =
     ``BHkv * ceil(group * nq / 256)`` workgroups are fewer than the 256 CUs leaves CUs idle.  Which to call (``docs/kv_prefill.md``, measured
     at ``BHkv = 8``, ``nk = 8192``): ``prefill_kv`` is 1.2 - 1.3x faster at ``group * nq = 8192`` (one workgroup per CU) and 1.4x SLOWER at
     ``group * nq = 4096`` (half the CUs); the crossover is near ``group * nq = 6000`` there, i.e. ``BHkv * group * nq`` of about 48 000 packed
-    rows.  Below it call ``forward_kv``.  No ``window_left``, no other head dim; fp8 caches: ``prefill_kv_fp8`` (``d = 128`` only).
+    rows.  Below it call ``forward_kv``.  No other head dim; fp8 caches: ``prefill_kv_fp8`` (``d = 128`` only).
 
     ``d = 256`` runs a kernel of its own with the same contract: a workgroup owns 128 packed rows (one 32-row block per wave), so the grid is
     ``BHkv * ceil(group * nq / 128)``.  Measured (``docs/kv_prefill_d256.md``, ``BHkv = 8``, group 4, causal): 0.43 - 0.58 of ``forward_kv``'s
     time at 256 and 512 workgroups (``nq`` 1024 and 2048, ``nk`` 2048 to 32768), 2.2x SLOWER at 64 workgroups; its time is flat up to one
     workgroup per CU while ``forward_kv``'s grows with the rows, and the two meet, interpolated, near 150 workgroups.  Call it from there on.
+
+    ``window_left`` (``include/flashattn_amd_kvpw.h``; ``None``: no window, the libraries above and their bits) is ``forward_kv``'s sliding
+    window on these kernels, at both head dims: row ``i`` sees key ``j`` iff ``j < len``, ``j >= len - nq + i - window_left`` and, when
+    ``causal``, ``j <= len - nq + i``.  An ``int >= 0`` (negative raises ``ValueError``; ``>= kv_len`` hides nothing and gives the bits of the
+    call without a window).  A tile walks only the 64-key blocks between its lowest row's first key and its widest row's last, so the time
+    follows ``window_left + nq``, not ``len``; with ``lo = max(0, len - nq - window_left)`` no K/V row below ``lo`` and none at or beyond
+    ``len`` is read, and such rows may hold anything.  ``docs/kv_prefill_window.md`` has the design and the measurements.
     """
+    window_left = _window(window_left)
     q, k, v, _, dims = _contiguous_cache(_BF16, q, k, v, kv_len, kv_lens)
-    return _run_prefill("prefill_kv", False, q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype)
+    return _run_prefill("prefill_kv", False, q, (k.data_ptr(), v.data_ptr()), dims, scale, causal, return_lse, out, out_dtype, (), window_left)
 
 
 def prefill_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
                   seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None, scale: float = 1.0, return_lse: bool = False,
-                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+                  out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, window_left: Optional[int] = None):
     """``prefill_kv`` over a paged cache: ``forward_paged``'s arguments and rules (pools never copied, pages of 16 .. 65536 rows, table and
     ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read) on the chunked-prefill kernel, ``d = 128`` or
-    ``d = 256`` (``prefill_kv`` says which library runs).  The result is ``prefill_kv``'s on the gathered cache, bit for bit."""
+    ``d = 256`` (``prefill_kv`` says which library runs).  The result is ``prefill_kv``'s on the gathered cache, bit for bit.
+
+    ``window_left`` (``None``: no window) is ``prefill_kv``'s: with ``lo = max(0, len - nq - window_left)`` no pool row of a key below ``lo`` or at
+    or beyond ``len`` is read, and no table entry of a page wholly below ``lo`` or at or beyond ``ceil(len / page)``: pages that have slid out
+    of the window can be freed or reused, and their entries may hold anything."""
+    window_left = _window(window_left)
     q, cache, shape = _paged_cache(_BF16, q, k_pool, v_pool, block_table, kv_len, seq_lens)
-    return _run_prefill("prefill_paged", True, q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype)
+    return _run_prefill("prefill_paged", True, q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype, (), window_left)
 
 
 def forward_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
@@ -537,7 +554,7 @@ def forward_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Ten
 
 def prefill_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: bool = False, *, k_scale: float = 1.0, v_scale: float = 1.0,
                    kv_len: Optional[int] = None, kv_lens: Optional[torch.Tensor] = None, scale: float = 1.0, return_lse: bool = False,
-                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, window_left: Optional[int] = None):
     """``prefill_kv`` over a cache of 8-bit floats (``include/flashattn_amd_kvp8.h``): chunked prefill against the cache ``forward_kv_fp8``
     decodes from, ``d = 128``.
 
@@ -551,22 +568,30 @@ def prefill_kv_fp8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, causal: 
     ``BHkv = 8``): ``prefill_kv_fp8`` is 1.15 - 1.4x faster than ``forward_kv_fp8`` at ``group * nq = 8192`` (one workgroup per CU; ``nk`` 2048
     to 32768, contiguous and paged) and 1.6x SLOWER at ``group * nq = 4096``; the crossover, interpolated, is near ``group * nq = 6500``
     there.  Call this entry when ``BHkv * ceil(group * nq / 256) >= 256``, ``forward_kv_fp8`` below.  It takes 1.04 - 1.07x the time of
-    ``prefill_kv`` on the dequantised cache.  No ``window_left``, no other head dim.
+    ``prefill_kv`` on the dequantised cache.  No other head dim.
+
+    ``window_left`` (``include/flashattn_amd_kvpw.h``; ``None``: no window) is ``prefill_kv``'s sliding window with its rules; rows below
+    ``lo = max(0, len - nq - window_left)`` are never read and may hold the NaN codes.  With ``v_scale`` a power of two the result is bit for bit
+    ``v_scale *`` that of ``prefill_kv`` on the dequantised cache with the same ``window_left``, and the LSE is that call's for any ``v_scale``.
     """
+    window_left = _window(window_left)
     q, k8, v8, _, dims = _contiguous_cache(_FP8, q, k8, v8, kv_len, kv_lens)
     return _run_prefill("prefill_kv_fp8", False, q, (k8.data_ptr(), v8.data_ptr()), dims, scale, causal, return_lse, out, out_dtype,
-                        (k_scale, v_scale))
+                        (k_scale, v_scale), window_left)
 
 
 def prefill_paged_fp8(q: torch.Tensor, k_pool8: torch.Tensor, v_pool8: torch.Tensor, block_table: torch.Tensor, causal: bool = False, *,
                       k_scale: float = 1.0, v_scale: float = 1.0, seq_lens: Optional[torch.Tensor] = None, kv_len: Optional[int] = None,
-                      scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+                      scale: float = 1.0, return_lse: bool = False, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                      window_left: Optional[int] = None):
     """``prefill_kv_fp8`` over paged pools of 8-bit floats: ``forward_paged_fp8``'s arguments and rules (pools never copied, strides multiples
     of 16 elements, pages of 16 .. 65536 rows, table and ``seq_lens`` read on the device only, no entry at or beyond ``ceil(len / page)`` read)
-    on the chunked-prefill kernel, ``d = 128``.  The result is ``prefill_kv_fp8``'s on the gathered bytes, bit for bit."""
+    on the chunked-prefill kernel, ``d = 128``.  The result is ``prefill_kv_fp8``'s on the gathered bytes, bit for bit.  ``window_left``
+    (``None``: no window) is ``prefill_paged``'s: no pool byte of a key below ``lo`` and no table entry of a page wholly below it is read."""
+    window_left = _window(window_left)
     q, cache, shape = _paged_cache(_FP8, q, k_pool8, v_pool8, block_table, kv_len, seq_lens)
     return _run_prefill("prefill_paged_fp8", True, q, (ctypes.byref(cache),), shape, scale, causal, return_lse, out, out_dtype,
-                        (k_scale, v_scale))
+                        (k_scale, v_scale), window_left)
 
 
 def forward_packed_qkv(inp: torch.Tensor, n_head: int) -> torch.Tensor:

@@ -29,7 +29,8 @@
  *             common accuracy, not bit for bit (other block boundaries per row); fa_kvp_paged_forward equals fa_kvp_forward on
  *             the gathered cache bit for bit.
  *
- * Out of scope (fp8 caches: include/flashattn_amd_kvp8.h): window_left, head dim 64 (256: include/flashattn_amd_kvp256.h), a key split for grids of a few workgroups (bh_kv * ceil(group *
+ * window_left is served by include/flashattn_amd_kvpw.h (libflashattn_amd_kvpw.so).
+ * Out of scope (fp8 caches: include/flashattn_amd_kvp8.h): head dim 64 (256: include/flashattn_amd_kvp256.h), a key split for grids of a few workgroups (bh_kv * ceil(group *
  * nq / 256) well below the 256 CUs), and routing from fa_kv_forward / fa_paged_forward, which keep their kernels and their bits.
  */
 #ifndef FLASHATTN_AMD_KVP_H

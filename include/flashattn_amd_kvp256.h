@@ -29,7 +29,8 @@
  *             bit for bit (other block boundaries per row); fa_kvp256_paged_forward equals fa_kvp256_forward on the gathered
  *             cache bit for bit.
  *
- * Out of scope: window_left, fp8 caches at this head dim, a key split for grids of a few workgroups (bh_kv * ceil(group * nq / 128)
+ * window_left is served by include/flashattn_amd_kvpw.h (libflashattn_amd_kvpw.so).
+ * Out of scope: fp8 caches at this head dim, a key split for grids of a few workgroups (bh_kv * ceil(group * nq / 128)
  * well below the 256 CUs), and routing from fa_kv256_forward / fa_kv256_paged_forward, which keep their kernels and their bits.
  */
 #ifndef FLASHATTN_AMD_KVP256_H

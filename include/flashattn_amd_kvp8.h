@@ -33,7 +33,8 @@
  *             fa_kvp8_forward on the gathered bytes, bit for bit; a V that is constant over the visible keys comes out as
  *             fp32(v_scale * constant).
  *
- * Out of scope: window_left, head dims 64 and 256, a key split for grids of a few workgroups, and routing from fa_kv8_forward /
+ * window_left is served by include/flashattn_amd_kvpw.h (libflashattn_amd_kvpw.so).
+ * Out of scope: head dims 64 and 256, a key split for grids of a few workgroups, and routing from fa_kv8_forward /
  * fa_kv8_paged_forward, which keep their kernels and their bits.
  */
 #ifndef FLASHATTN_AMD_KVP8_H
